@@ -9,8 +9,13 @@ table: scan kernel + per-workgroup table fold (+ the SUM/MAX all-reduce of the p
 tables over RCCL when N > 1) + finalize on rank 0.  Inputs are resident in HBM before the
 timed region.  The 1 B rows are block-sharded across the N ranks (strong scaling).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--workload NAME]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--rows R] [--workload NAME] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps of the headline and prints its line.  --full adds everything else
+the record has carried: the canonical-storage phase, the full-size oracle check, the CPU baselines, configs 1 / 2 / 4 / 5,
+the disk -> HBM load and cold CLI figures, and config 4's extra legs (the --no-* switches trim a --full run).
+--dump-outputs DIR writes the last timed step's result as DIR/<name>.npy (float64; see result_arrays).
 """
 import argparse
 import json
@@ -23,6 +28,63 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 achievable by a copy
+DUMP_LIMIT_BYTES = 64 << 20
+AGG_FIELDS = ("present", "count", "samples", "sum", "avg", "stddev", "min", "max", "bucket_size", "num_buckets", "n_outliers")
+
+
+def result_arrays(res, q):
+    """What a caller of the timed path receives from a step: the result's rows (time rows for a time query), ordered by
+    (time bucket, group key) so that two builds compare row for row, as float64 arrays -- the group keys (one column per
+    group-by), Count, Samples, every aggregation's scalar fields, and its bucket counts / percentiles for the rows that carry
+    them (<agg>_values / <agg>_percentiles / <agg>_outlier_values, with the row each belongs to in <agg>_<array>_rows, and
+    <agg>_<array>_lengths when they differ in length).  When everything would exceed DUMP_LIMIT_BYTES, a fixed seeded
+    sample of the rows is kept; row_index says which."""
+    import numpy as np
+    which = 1 if q.get("time_col") else 0
+    rows = res.rows(which, want_values=True)
+    n_groups = res.n_groups
+    rows.sort(key=lambda r: (r["time_bucket"], np.frombuffer(r["key"], dtype="<i8").tolist()))
+    aggs = list(q.get("aggs", ()))
+    arrays = ("values", "percentiles", "outlier_values")
+
+    def row_bytes(r):
+        return 8 * (4 + n_groups + len(aggs) * len(AGG_FIELDS) + sum(len(h.get(k, ())) + 2 for h in r["hists"] for k in arrays))
+
+    keep = np.arange(len(rows))
+    sizes = np.array([row_bytes(r) for r in rows], dtype=np.int64)
+    budget = DUMP_LIMIT_BYTES - (1 << 20)  # (the .npy headers and the per-result scalars)
+    if sizes.sum() > budget:
+        order = np.random.default_rng(0).permutation(len(rows))
+        keep = np.sort(order[:int(np.searchsorted(np.cumsum(sizes[order]), budget, side="right"))])
+    rows = [rows[i] for i in keep]
+    out = {"matched": np.array([res.matched], dtype=np.float64), "row_index": keep.astype(np.float64),
+           "count": np.array([r["count"] for r in rows], dtype=np.float64),
+           "samples": np.array([r["samples"] for r in rows], dtype=np.float64)}
+    if which == 1:
+        out["time_bucket"] = np.array([r["time_bucket"] for r in rows], dtype=np.float64)
+    if n_groups:
+        out["key"] = np.frombuffer(b"".join(r["key"] for r in rows), dtype="<i8").reshape(len(rows), n_groups).astype(np.float64)
+    for a, name in enumerate(aggs):
+        for f in AGG_FIELDS:
+            out["%s_%s" % (name, f)] = np.array([r["hists"][a][f] for r in rows], dtype=np.float64)
+        for arr in arrays:
+            have = [i for i, r in enumerate(rows) if arr in r["hists"][a]]
+            if have:
+                parts = [rows[i]["hists"][a][arr] for i in have]
+                out["%s_%s_rows" % (name, arr)] = np.array(have, dtype=np.float64)
+                if len({len(p) for p in parts}) == 1:
+                    out["%s_%s" % (name, arr)] = np.stack(parts).astype(np.float64)
+                else:
+                    out["%s_%s" % (name, arr)] = np.concatenate(parts).astype(np.float64)
+                    out["%s_%s_lengths" % (name, arr)] = np.array([len(p) for p in parts], dtype=np.float64)
+    return out
+
+
+def write_outputs(directory, arrays):
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float64))
 
 
 def cpu_baseline(workload, total_rows, budget_s=20.0):
@@ -265,7 +327,14 @@ def main():
                     help="only the headline workload: skip the cfg2 / cfg4 / cfg5 records of the `configs` key")
     ap.add_argument("--no-oracle-check", action="store_true",
                     help="skip the full-size bit-exact check of the result against the CPU oracle (N=1 only)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: canonical storage, the oracle check, CPU baselines, the other configs, the "
+                         "load / cold CLI figures and config 4's extra legs (each still trimmed by its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's result as DIR/<name>.npy (float64, at most 64 MB in all)")
     args = ap.parse_args()
+    if not args.full:
+        args.no_canonical = args.no_oracle_check = args.no_cpu_baseline = args.no_configs = args.no_load = True
 
     import torch
     import torch.distributed as dist
@@ -330,7 +399,7 @@ def main():
             "cfg2_group1_avg2": "group-by 1 low-card col, sum+avg of 2 cols",
             "cfg1_count_range": "count(*) with one int-range predicate"}
 
-    def measure(workload, total_rows, steps, warmup, storage, canonical_too):
+    def measure(workload, total_rows, steps, warmup, storage, canonical_too, dump=False):
         """One BASELINE workload: builds this rank's shard of the synthetic table, times `steps` steps (after `warmup`)
         in `storage`, optionally the same table in canonical int64 storage first.  Returns the record rank 0 prints."""
         wl = synth.WORKLOADS[workload]
@@ -354,7 +423,7 @@ def main():
             hi = a + 4 * (b - 1) if kind == synth.BELL else a + b - 1
             table.set_bounds(n, a, hi)
 
-        def run_phase(steps, warmup):
+        def run_phase(steps, warmup, dump=False):
             """Prepares the query against the table as currently laid out, does `warmup` untimed steps and
             times exactly `steps` steps (barrier + synchronize on both sides, max over ranks).
 
@@ -464,6 +533,8 @@ def main():
                 if workload == "cfg4_hist_highcard":
                     out["printed"] = res.render("text")  # (what the CLI's text printer shows of this result)
                 out["digest"] = sorted((g["time_bucket"], g["key"], g["count"]) + tuple(h["sum"] for h in g["hists"]) for g in rows_out)
+                if dump:
+                    out["dump"] = result_arrays(res, q)
                 res.free()
             for qy in queries:
                 qy.free()
@@ -496,9 +567,10 @@ def main():
             canon = run_phase(min(steps, 10), min(warmup, 2))
         if storage == "compact":
             table.compact()
-        head = run_phase(steps, warmup)
+        head = run_phase(steps, warmup, dump)
+        dumped.update(head.pop("dump", {}))
         extra = {}
-        if workload == "cfg4_hist_highcard" and q.get("printed_only"):
+        if workload == "cfg4_hist_highcard" and q.get("printed_only") and args.full:
             q["printed_only"] = False
             alt = run_phase(min(steps, 10), warmup)  # (the same warm-up: its first steps allocate the pinned 52 MB percentile buffers)
             q["printed_only"] = True
@@ -514,7 +586,7 @@ def main():
                                                  "host_ms_per_step": alt["host_ms"], "rows_first_access_ms": alt.get("rows_first_access_ms"),
                                                  "what": "the same step with percentiles / stddev derived for all 65 536 groups (k_hist_summary over the "
                                                          "525 MB table + 52 MB of percentiles to the host per step): what -encode-results needs"}
-        if workload == "cfg4_hist_highcard" and q.get("printed_only") and world == 1:
+        if workload == "cfg4_hist_highcard" and q.get("printed_only") and world == 1 and args.full:
             # -limit pushed INTO the scan (sybl_query_desc.printed_only = 2, csrc/pushdown.hip): the printer's query when the
             # rows beyond the limit need nothing but their Count -- group counts from the key column, the printed groups chosen
             # on the device, one pass over key + value for Cumulative and those groups.  A SEPARATE, labelled measurement: never
@@ -540,7 +612,7 @@ def main():
                                    "what": "the counting pass over the key column (k_count*: per-(workgroup, bin) record counts) runs in a prepared "
                                            "query's FIRST scan; rescans of the unchanged table reuse its regions, as they reuse block statistics "
                                            "(SYBL_NO_COUNT_CACHE=1: every scan) -- the timed steps are rescans"}
-        if workload == "cfg4_hist_highcard":
+        if workload == "cfg4_hist_highcard" and args.full:
             # scans back to back (no finalize between them: the GPU never idles, clocks stay up): the kernels' own figure
             qy = table.query(**q)
             ms = []
@@ -590,8 +662,11 @@ def main():
         table.free()
         return out
 
-    out = measure(args.workload, args.rows, args.steps, args.warmup, args.storage, not args.no_canonical)
+    dumped = {}  # (the headline's last timed step, as result_arrays lays it out: rank 0 only)
+    out = measure(args.workload, args.rows, args.steps, args.warmup, args.storage, not args.no_canonical, dump=bool(args.dump_outputs))
     if rank == 0:
+        if args.dump_outputs:
+            write_outputs(args.dump_outputs, dumped)
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"], columnar = cpu_baseline(args.workload, args.rows or synth.WORKLOADS[args.workload]["rows"])
             if columnar is not None:

@@ -35,7 +35,7 @@ def test_bench_line_from_n_ranks_on_one_device(world, workload, rows):
     env = dict(os.environ, LD_PRELOAD=STANDIN, SYBL_BENCH_ONE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0", SYBL_STANDIN_TIMEOUT_S="240")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(world), "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), "bench.py", "--gpus", str(world), "--steps", "4", "--warmup", "2", "--workload", workload,
-           "--rows", str(rows), "--no-cpu-baseline", "--no-load", "--no-configs", "--no-canonical"]
+           "--rows", str(rows), "--full", "--no-cpu-baseline", "--no-load", "--no-configs", "--no-canonical"]
     p = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

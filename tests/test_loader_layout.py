@@ -157,7 +157,8 @@ def test_damaged_blocks_under_the_sanitizers(table, tmp_path):
     load (SYBL_LOADER_GPU_VARINT=1: slices located and copied as file bytes instead of decoded)."""
     root, _ = table
     exe = str(tmp_path / "loader_block_fuzz")
-    b = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O1", "-g", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-std=c++17", "-x", "hip",
+    b = subprocess.run(["hipcc", "--offload-arch=gfx950", "-O1", "-g", "-Xarch_host", "-fsanitize=address,undefined", "-fno-omit-frame-pointer", "-std=c++17",
+                        "-x", "hip",
                         os.path.join(ROOT, "tools", "micro", "loader_block_fuzz.cpp"), "-o", exe, "-I", os.path.join(ROOT, "sybil_amd", "csrc"),
                         "-I", os.path.join(ROOT, "include"), "-L", os.path.join(ROOT, "sybil_amd"), "-lsybilgpu",
                         "-Wl,-rpath," + os.path.join(ROOT, "sybil_amd"), "-Wl,-rpath,/opt/rocm/lib"], capture_output=True, text=True, timeout=900)

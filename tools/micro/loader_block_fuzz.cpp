@@ -3,7 +3,7 @@
 // inserted, removed, the tail cut off, a huge length planted, the file removed), and the block prepared into a heap slab of
 // exactly the size load_blocks gives a worker.  Nothing is checked but that the call returns a verdict -- build with the
 // sanitizers so that a write past the slab or a read past a decoded array stops the run:
-//   hipcc --offload-arch=gfx950 -O1 -g -fsanitize=address,undefined -std=c++17 -x hip loader_block_fuzz.cpp -o loader_block_fuzz \
+//   hipcc --offload-arch=gfx950 -O1 -g -Xarch_host -fsanitize=address,undefined -std=c++17 -x hip loader_block_fuzz.cpp -o loader_block_fuzz \
 //         -I../../sybil_amd/csrc -I../../include -L../../sybil_amd -lsybilgpu -Wl,-rpath,$PWD/../../sybil_amd -Wl,-rpath,/opt/rocm/lib
 //   ./loader_block_fuzz <block dir> <scratch dir> <trials> name:type ...        (type: 1 int, 2 str, 3 set)
 // SYBL_LOADER_TWO_PASS=1: the two-pass form of every block.  SYBL_LOADER_GPU_VARINT=1: the worker half of the default load.
