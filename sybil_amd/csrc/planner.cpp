@@ -1554,6 +1554,9 @@ struct Planner {
         };
         const int sum_bits = std::max(1, bits(umax * slot_rows)), count_bits = bits(slot_rows);
         if (sum_bits + count_bits <= 64 && sum_bits < 63) FP.cshift = sum_bits;
+        // SYBL_PLAN_TRACE=1 (diagnostic): the decision and the widths behind it, also when they do not fit (cshift=0)
+        if (env("SYBL_PLAN_TRACE"))
+            fprintf(stderr, "count packing: cshift=%d sum_bits=%d count_bits=%d slot_rows=%lld\n", (int)FP.cshift, sum_bits, count_bits, (long long)slot_rows);
     }
 
     // -limit pushed into the scan (pushdown.hip).  Taken when the caller said the rows beyond the limit need nothing but their

@@ -86,8 +86,10 @@ def test_pushed_down_printer_prints_what_the_full_path_prints(ctx, oracle, rows,
 
 
 def test_a_hot_group_fills_its_counter_field_many_times(ctx, oracle):
-    """Skew: one key holds a third of the rows, so its 15-bit LDS counter wraps dozens of times per workgroup (the guard bit
-    and the device-side carries); a range of keys never occurs."""
+    """Skew: one key holds a third of the rows and a range of keys never occurs.  The 15-bit LDS counter of the hot key wraps
+    (the guard bit and the device-side carries) only where ONE workgroup sees more than 32 767 of its rows: the planner deals
+    the rows out evenly over one workgroup per CU, so that takes a device of at most 40 CUs here -- on one with hundreds each
+    workgroup sees about 5 000 of them and no field fills.  The wraps themselves are test_gpu_word_packing.py's business."""
     rng = np.random.default_rng(3)
     n = 4_000_000
     key = rng.integers(0, 40_000, n)
