@@ -42,7 +42,7 @@
 extern "C" {
 #endif
 
-#define SYBL_ABI_VERSION 5
+#define SYBL_ABI_VERSION 6
 
 enum {
     SYBL_OK = 0,
@@ -340,7 +340,8 @@ void sybl_query_free(sybl_query *q);
 int sybl_query_scan(sybl_query *q);
 
 /* The rank-local partial group table, laid out identically on every rank of a job:
- * `sum` words combine with SUM, `max` words with MAX (minima are stored negated).
+ * `sum` words combine with SUM, `max` words with MAX (minima are stored as their bitwise
+ * complement ~v since ABI 6: like -v it reverses the order, and it has no overflow at INT64_MIN).
  * Multi-GPU hosts all-reduce both buffers in place (RCCL over xGMI) between
  * sybl_query_scan and sybl_query_finalize; single-GPU hosts skip this. */
 int sybl_query_partials(sybl_query *q, void **d_sum, int64_t *n_sum_words, void **d_max, int64_t *n_max_words);
@@ -419,8 +420,12 @@ typedef struct {
     int32_t present;      /* 0: this group never saw an INT value for the aggregation */
     int64_t count;        /* BasicHist.Count (weighted) */
     int64_t samples;      /* BasicHist.Samples */
-    int64_t sum;          /* exact  sum(v*w)  over accepted values */
-    double avg;           /* sum/count      (reference: running mean, <=1e-6 rel) */
+    int64_t sum;          /* the LOW 64 BITS of the exact  sum(v*w)  over accepted values (a group of 5 400 microsecond
+                           * timestamps already leaves int64) */
+    double avg;           /* true sum/count (reference: running mean, <=1e-6 rel).  The true sum is recovered from `sum`, the
+                           * count n and the bounds [lo, hi] of the accepted values while n*(hi - lo) < 2^64 (the group's own
+                           * extrema where they are tracked, then (n-2)*(hi - lo); else the column's); beyond that -- four rows
+                           * of 9e18 next to one of -4e18 -- avg, stddev and the printed sum come from the wrapped sum */
     double stddev;        /* GetStdDev semantics (hist_basic.go:192-219); 0 in AVG mode */
     int64_t min, max;     /* BasicHist.Min/Max incl. the reference's initial values */
     int64_t bucket_size;  /* HIST: BasicHist.BucketSize */

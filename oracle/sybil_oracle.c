@@ -54,6 +54,7 @@ struct orc_hist {
     int weight_mode;
     /* exact side-state (what an order-independent integer engine computes) */
     uint64_t sum_exact;
+    __int128 sum_wide; /* the same sum without the wrap: |v*w| < 2^126, so 128 bits hold any table's */
     int64_t true_min, true_max;
     i64vec all_outliers, all_underliers; /* merged across blocks */
     /* MultiHist (hist_multi.go:6-19): the fields above are its Max / Min / Samples / Count / Avg / Info; values,
@@ -282,6 +283,7 @@ void orc_hist_add(orc_hist *h, int64_t value, int64_t weight) {
     {
         int64_t w_applied = (h->weight_mode || weight > 1) ? weight : 1;
         h->sum_exact += (uint64_t)value * (uint64_t)w_applied;
+        h->sum_wide += (__int128)value * (__int128)w_applied;
         if (value < h->true_min) h->true_min = value;
         if (value > h->true_max) h->true_max = value;
     }
@@ -333,6 +335,7 @@ void orc_hist_combine(orc_hist *h, const orc_hist *o) {
     h->count = total;
     /* exact side-state */
     h->sum_exact += o->sum_exact;
+    h->sum_wide += o->sum_wide;
     if (o->true_min < h->true_min) h->true_min = o->true_min;
     if (o->true_max > h->true_max) h->true_max = o->true_max;
     for (int64_t i = 0; i < o->all_outliers.n; i++) vec_push(&h->all_outliers, o->all_outliers.v[i]);
@@ -387,6 +390,12 @@ double orc_stddev_from_values(const int64_t *values, int64_t n_values, int64_t b
     return sqrt(sum_variance);
 }
 
+/* the exact mean: from the 128-bit sum (sum_exact alone wraps once a group's sum leaves int64 -- some 5 400 rows of a
+ * microsecond timestamp) */
+static double hist_avg_exact(const orc_hist *h) {
+    return h->count ? (double)((long double)h->sum_wide / (long double)h->count) : 0.0;
+}
+
 void orc_hist_info_get(const orc_hist *h, orc_hist_info *out) {
     memset(out, 0, sizeof(*out));
     out->present = 1;
@@ -413,7 +422,7 @@ void orc_hist_info_get(const orc_hist *h, orc_hist_info *out) {
             out->n_outliers += h->sub[i]->all_outliers.n;
             out->n_underliers += h->sub[i]->all_underliers.n;
         }
-        const double avg_exact = h->count ? (double)((long double)(int64_t)h->sum_exact / (long double)h->count) : 0.0;
+        const double avg_exact = hist_avg_exact(h);
         out->stddev_ref = h->percentile_mode ? multi_stddev(h, h->avg) : 0.0;
         out->stddev_exact = h->percentile_mode ? multi_stddev(h, avg_exact) : 0.0;
         return;
@@ -421,7 +430,7 @@ void orc_hist_info_get(const orc_hist *h, orc_hist_info *out) {
     out->stddev_ref = orc_stddev_from_values(h->values, h->n_values, h->bucket_size, h->min, h->count, h->avg,
                                              h->outliers.v, h->outliers.n, h->underliers.v, h->underliers.n);
     {
-        double avg_exact = h->count ? (double)((long double)(int64_t)h->sum_exact / (long double)h->count) : 0.0;
+        double avg_exact = hist_avg_exact(h);
         out->stddev_exact = orc_stddev_from_values(h->values, h->n_values, h->bucket_size, h->min, h->count,
                                                    avg_exact, h->all_outliers.v, h->all_outliers.n,
                                                    h->all_underliers.v, h->all_underliers.n);

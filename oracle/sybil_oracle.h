@@ -149,13 +149,13 @@ typedef struct {
     int64_t samples;      /* h.Samples */
     int64_t min, max;     /* h.Min / h.Max incl. the reference's initial values */
     double avg;           /* reference-order running / merged mean */
-    int64_t sum_exact;    /* exact Σ v*w over accepted values (wraps mod 2^64) */
+    int64_t sum_exact;    /* exact Σ v*w over accepted values: its low 64 bits (wraps mod 2^64) */
     int64_t true_min, true_max; /* extrema over accepted values only */
     int64_t n_outliers;   /* accepted values clipped into the last bucket (all blocks) */
     int64_t n_underliers;
     double stddev_ref;    /* GetStdDev on the merged hist as the reference would hold it
                              (outlier list of the first block only, hist_basic.go:259-279) */
-    double stddev_exact;  /* GetStdDev with avg = sum_exact/count and every outlier */
+    double stddev_exact;  /* GetStdDev with avg = (128-bit Σ v*w)/count and every outlier */
 } orc_hist_info;
 int orc_result_hist(const orc_results *r, int which, int64_t idx, int agg, orc_hist_info *out);
 /* Result.Distinct.Cardinality() (printer.go:79-80,142-144,204-205); regs_out (ORC_LLB_M bytes, may be NULL) receives

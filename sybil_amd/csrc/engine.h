@@ -370,6 +370,7 @@ struct AggInfo {
     int32_t f_out;  // base of 6 outlier fields (n, sum, sq limb0..3) or -1
     int64_t num_buckets;
     int64_t info_max;
+    int64_t vlo, vhi;  // every accepted value lies in [vlo, vhi] (vlo > vhi: none can be accepted); result.cpp: true_sum
     std::vector<sybl_subhist> subs;  // -loghist: the sub-histograms (layout of the aggregation's bucket words)
 };
 

@@ -78,7 +78,7 @@ __global__ __launch_bounds__(T) void k_scan_hash_packed(const FastPlan P, uint64
                     fast_max64<LDS>(maxtab, (uint64_t)(uint32_t)P.m_max[c] * ncell + slot, x);
                 } else {
                     if (P.m_max[c] >= 0) fast_max64<LDS>(maxtab, (uint64_t)(uint32_t)P.m_max[c] * ncell + slot, x);
-                    if (P.m_nmin[c] >= 0) fast_max64<LDS>(maxtab, (uint64_t)(uint32_t)P.m_nmin[c] * ncell + slot, x == INT64_MIN ? INT64_MAX : -x);
+                    if (P.m_nmin[c] >= 0) fast_max64<LDS>(maxtab, (uint64_t)(uint32_t)P.m_nmin[c] * ncell + slot, ~x);
                 }
             }
             if (MODE == kFastMoments) {

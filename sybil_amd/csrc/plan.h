@@ -97,7 +97,7 @@ struct AggDesc {
     int32_t f_out;        // 6 fields: n, sum(o), sum(o^2) as four 32-bit limbs -- only when the
                           // column's bounds allow a value to land beyond the last bucket
     int32_t m_max;        // MAX-section field: max(v)
-    int32_t m_nmin;       // MAX-section field: max(-v)
+    int32_t m_nmin;       // MAX-section field: max(~v) = ~min(v)
     int32_t hist_full;    // 1: bucket arrays in the SUM section (global atomics)
     int32_t multi_n;      // -loghist: sub-histograms of this aggregation (0 = BasicHist), ScanPlan::multi[multi_off ..]
     int32_t multi_off;

@@ -1167,6 +1167,9 @@ struct Planner {
             ai.f_out = -1;
             ai.num_buckets = 0;
             ai.info_max = imax;
+            // accepted values lie in [max(lo,imin), min(hi,max10)]
+            ai.vlo = empty ? imin : std::max(lo, imin);
+            ai.vhi = empty ? imin : std::min(hi, A.max10);
             if (d->op == SYBL_AGG_HIST && q->loghist) {
                 // MultiHist.TrackPercentiles, hist_multi.go:223-257: sub-histograms over ranges that halve from Info.Max
                 // downwards until one is at most NUM_BUCKETS wide, the last one from Info.Min to the left edge reached
@@ -1242,8 +1245,7 @@ struct Planner {
                 A.inv_bucket = 1.0 / (double)bs;
                 A.n_values = (int32_t)nv;
                 ai.num_buckets = nb;
-                // accepted values lie in [max(lo,imin), min(hi,max10)]
-                int64_t vhi = empty ? imin : std::min(hi, A.max10), vlo = empty ? imin : std::max(lo, imin);
+                const int64_t vhi = ai.vhi, vlo = ai.vlo;
                 unsigned __int128 span = vhi >= A.hmin ? (unsigned __int128)((__int128)vhi - (__int128)A.hmin) : 0;
                 A.big_div = span >= ((unsigned __int128)1 << 51);
                 bool can_outlie = span / (unsigned __int128)bs >= (unsigned __int128)nv || vlo < A.hmin;

@@ -5,7 +5,7 @@
 // reference's only multi-node mechanism ships gob files to `sybil aggregate`
 // (node_aggregator.go:147-177).  Here every rank holds an identically laid out integer
 // table, so the merge is one SUM all-reduce (counts, sums, buckets) plus one MAX
-// all-reduce (extrema; minima are stored negated) over RCCL / xGMI.
+// all-reduce (extrema; minima are stored complemented, ~v) over RCCL / xGMI.
 #include <dlfcn.h>
 #include <stdlib.h>
 #include <string.h>

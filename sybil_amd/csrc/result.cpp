@@ -44,6 +44,38 @@ static void percentiles_from_values(const int64_t *values, int64_t n_values, int
     memcpy(out100, pct, 100 * sizeof(int64_t));
 }
 
+// The true sum(v*w) of a cell from the 64 bits the scan (and a cross-rank SUM) keeps of it.  Every reader of a cell's sum
+// goes through here: agg_finish (avg, stddev, and through avg the sum the renderers print) and the sort by mean.
+//
+// The n = Count units of weight of the cell each carry a value in [lo, hi], so T - n*lo lies in [0, n*(hi - lo)]; while that
+// width is below 2^64 it IS (S - n*lo) mod 2^64.  `anchored`: lo and hi are the cell's own extrema, each carried by one unit
+// at least, which leaves (n - 2)*(hi - lo) for the rest (two rows at INT64_MIN and 5 are exact that way).  Beyond the bound
+// (and for weights below 1) the wrapped sum is all there is: the limit DESIGN.md and include/sybilgpu.h state.
+static __int128 true_sum(uint64_t S, int64_t n, int64_t lo, int64_t hi, bool anchored) {
+    const __int128 wrapped = (__int128)(int64_t)S;
+    if (n <= 0 || lo > hi) return wrapped;
+    const __int128 span = (__int128)hi - (__int128)lo;
+    const bool anch = anchored && n >= 2;
+    const __int128 base = anch ? (__int128)lo + (__int128)hi + (__int128)(n - 2) * (__int128)lo : (__int128)n * (__int128)lo;
+    const unsigned __int128 width = (unsigned __int128)(anch ? n - 2 : n) * (unsigned __int128)span;
+    if (width >> 64) return wrapped;
+    const unsigned __int128 off = (uint64_t)(S - (uint64_t)base);
+    return off <= width ? base + (__int128)off : wrapped;  // (outside [base, base + width]: the bounds do not describe this cell)
+}
+
+// [lo, hi] of true_sum for a cell: the planner's bounds of the accepted values, narrowed by the extrema the cell tracked
+static __int128 true_sum(const AggInfo &ai, uint64_t S, int64_t n, bool has_max, int64_t vmax, bool has_nmin, int64_t nmin) {
+    int64_t lo = ai.vlo, hi = ai.vhi;
+    if (n > 0 && has_max) hi = std::min(hi, vmax);
+    if (n > 0 && has_nmin) lo = std::max(lo, ~nmin);
+    return true_sum(S, n, lo, hi, has_max && has_nmin);
+}
+
+static __int128 true_sum(const AggInfo &ai, const AggAcc &a, int64_t cnt) {
+    if (a.wide) return a.wide_sum;
+    return true_sum(ai, a.sum, cnt, ai.d.m_max >= 0, a.vmax, ai.d.m_nmin >= 0, a.nmin);
+}
+
 // (Q: what the row builders read of the query -- op, weighted, loghist, want_percentiles, aggs: FinCtx, the result's own copy)
 template <class Q>
 static void agg_finish(const Q *q, Result *R, const AggInfo &ai, const AggAcc &a, int64_t row_count, sybl_agg_out &o,
@@ -60,9 +92,9 @@ static void agg_finish(const Q *q, Result *R, const AggInfo &ai, const AggAcc &a
     o.count = cnt;
     o.samples = q->weighted ? a.smp : 0;  // BasicHist.Samples only moves with a weight column (hist_basic.go:111-116)
     o.sum = (int64_t)a.sum;
-    long double avg_l = cnt != 0 ? (long double)(int64_t)a.sum / (long double)cnt : 0.0L;
+    long double avg_l = cnt != 0 ? (long double)true_sum(ai, a, cnt) / (long double)cnt : 0.0L;
     o.avg = (double)avg_l;
-    int64_t tmax = a.vmax, tmin = a.nmin == INT64_MIN ? INT64_MAX : -a.nmin;
+    int64_t tmax = a.vmax, tmin = ~a.nmin;  // (nothing seen: ~INT64_MIN = INT64_MAX)
     if (q->op == SYBL_AGG_HIST) {
         o.min = std::min(A.info_min, tmin);   // SetupBuckets: h.Min = Info.Min
         o.max = std::max(ai.info_max, tmax);  //               h.Max = Info.Max
@@ -945,7 +977,10 @@ int query_finalize(Query *q, Result **out) {
             const int64_t pop = A.f_pop >= 0 ? F[(int64_t)A.f_pop * ncell + cell] : (P.f_samples >= 0 ? samples : count);
             if (pop <= 0) return -INFINITY;
             const int64_t cnt = A.f_cnt >= 0 ? F[(int64_t)A.f_cnt * ncell + cell] : count;
-            const long double avg_l = cnt != 0 ? (long double)F[(int64_t)A.f_sum * ncell + cell] / (long double)cnt : 0.0L;
+            const __int128 T = true_sum(q->aggs[(size_t)by], (uint64_t)F[(int64_t)A.f_sum * ncell + cell], cnt, A.m_max >= 0,
+                                        A.m_max >= 0 ? hm[(int64_t)A.m_max * ncell + cell] : 0, A.m_nmin >= 0,
+                                        A.m_nmin >= 0 ? hm[(int64_t)A.m_nmin * ncell + cell] : 0);
+            const long double avg_l = cnt != 0 ? (long double)T / (long double)cnt : 0.0L;
             return (double)avg_l;
         };
         std::vector<uint32_t> &order = R->order0;
@@ -1170,6 +1205,8 @@ void result_ensure_rows(Result *R) {
                     d.smp += s.smp;
                     d.pop += s.pop;
                     d.sum += s.sum;
+                    d.wide_sum += true_sum(C.aggs[a], s, s.cnt);
+                    d.wide = true;
                     d.sb += s.sb;
                     d.sb2 += s.sb2;
                     d.n_out += s.n_out;
@@ -1225,6 +1262,8 @@ void result_ensure_rows(Result *R) {
                 d.smp += s2.smp;
                 d.pop += s2.pop;
                 d.sum += s2.sum;
+                d.wide_sum += s2.wide_sum;
+                d.wide = d.wide || s2.wide;
                 d.sb += s2.sb;
                 d.sb2 += s2.sb2;
                 d.n_out += s2.n_out;
@@ -1242,6 +1281,9 @@ void result_ensure_rows(Result *R) {
     if (C.pushdown)  // (the cells beyond the limit carry no sums: Cumulative's come from the scan's own totals over every row)
         for (size_t a = 0; a < na; a++) {
             total.aggs[a].sum = (uint64_t)C.pd_sum[a];
+            // (64 bits over every row, recovered from the planner's bounds alone: the cells beyond the limit brought no extrema)
+            total.aggs[a].wide_sum = true_sum((uint64_t)C.pd_sum[a], total.aggs[a].cnt, C.aggs[a].vlo, C.aggs[a].vhi, false);
+            total.aggs[a].wide = true;
             total.aggs[a].vmax = C.aggs[a].d.m_max >= 0 ? C.pd_max[a] : total.aggs[a].vmax;
         }
     size_t next_slot = live.size();

@@ -16,11 +16,14 @@ struct AggAcc {
     bool moments = false;              // sb / sb2 are valid even though the query keeps bucket arrays
     int64_t cnt = 0, smp = 0, pop = 0;
     uint64_t sum = 0;
+    // Cumulative only: the cells' true sums added up in 128 bits (true_sum in result.cpp); `sum` stays their low 64 bits
+    bool wide = false;
+    __int128 wide_sum = 0;
     int64_t sb = 0, sb2 = 0;
     int64_t n_out = 0;
     uint64_t sum_out = 0;
     uint64_t sq[4] = {0, 0, 0, 0};
-    int64_t vmax = INT64_MIN, nmin = INT64_MIN;
+    int64_t vmax = INT64_MIN, nmin = INT64_MIN;  // nmin: max(~v), i.e. ~min(v); INT64_MIN in either: no value seen
     const int64_t *values = nullptr;  // bucket counts (full-hist mode), n_values long
 };
 

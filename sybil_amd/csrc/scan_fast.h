@@ -46,7 +46,7 @@ struct FastPlan {
     int32_t n_values[kFastMaxA];
     int32_t f_sum[kFastMaxA], f_sb[kFastMaxA], f_sb2[kFastMaxA], m_max[kFastMaxA];
     // avg mode over a column with negative values tracks a MINIMUM too (BasicHist.Min starts at Go's zero value,
-    // hist_basic.go:72-85), as max(-v); and an aggregation whose values never exceed 0 tracks no maximum.  ext_general says
+    // hist_basic.go:72-85), as max(~v); and an aggregation whose values never exceed 0 tracks no maximum.  ext_general says
     // that some aggregation of a kFastAvgMax query departs from "every aggregation tracks a maximum and nothing else":
     // the row bodies then test m_max / m_nmin per aggregation (wave-uniform) instead of assuming it (round 5: such
     // queries used to run the plan interpreter).
@@ -496,7 +496,7 @@ __device__ __forceinline__ void fast_accumulate(const FastPlan &P0, const FastTi
                 fast_max64<LDS>(maxtab, (((uint64_t)(uint32_t)P.m_max[c] * ncell) << rs) + cidx, x);
             } else {
                 if (P.m_max[c] >= 0) fast_max64<LDS>(maxtab, (((uint64_t)(uint32_t)P.m_max[c] * ncell) << rs) + cidx, x);
-                if (P.m_nmin[c] >= 0) fast_max64<LDS>(maxtab, (((uint64_t)(uint32_t)P.m_nmin[c] * ncell) << rs) + cidx, x == INT64_MIN ? INT64_MAX : -x);
+                if (P.m_nmin[c] >= 0) fast_max64<LDS>(maxtab, (((uint64_t)(uint32_t)P.m_nmin[c] * ncell) << rs) + cidx, ~x);
             }
         }
         if (MODE == kFastMoments || MODE == kFastHist) {

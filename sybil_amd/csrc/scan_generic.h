@@ -290,7 +290,7 @@ __device__ __forceinline__ void row_accumulate(CPlan &P, const Tile<NC> &t, int 
         if (A.f_cnt >= 0) acc_add<USE_LDS>(sumtab, ((int64_t)A.f_cnt * ncell << rs) + cidx, w);
         if (A.f_smp >= 0) acc_add<USE_LDS>(sumtab, ((int64_t)A.f_smp * ncell << rs) + cidx, 1);
         if (A.m_max >= 0) acc_max<USE_LDS>(maxtab, ((int64_t)A.m_max * ncell << rs) + cidx, x);
-        if (A.m_nmin >= 0) acc_max<USE_LDS>(maxtab, ((int64_t)A.m_nmin * ncell << rs) + cidx, x == INT64_MIN ? INT64_MAX : -x);
+        if (A.m_nmin >= 0) acc_max<USE_LDS>(maxtab, ((int64_t)A.m_nmin * ncell << rs) + cidx, ~x);
         if (P.hist_mode && A.multi_n > 0) {
             // -loghist: the first sub-histogram whose range holds the value (hist_multi.go:84-89)
             int64_t *H = P.sum_out + P.hist_off + gcell * P.hist_stride + P.hist_agg_off[s.agg_index];

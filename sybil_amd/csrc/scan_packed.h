@@ -352,7 +352,7 @@ __device__ __forceinline__ void packed_row(const FastPlan &P0, const PackedTile<
                 }
                 if (P.m_nmin[c] >= 0) {
                     int64_t *m = (int64_t *)(cell_p + ((uint32_t)P.n_sum_fields + (uint32_t)P.m_nmin[c]) * fstep);
-                    const int64_t nx = x == INT64_MIN ? INT64_MAX : -x;
+                    const int64_t nx = ~x;
                     if (nx > *m) __hip_atomic_fetch_max(m, nx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
             }

@@ -766,13 +766,25 @@ int column_install_gdict(Table *t, Column *c) {
     while ((size_t)cap < 2 * D + 2) cap <<= 1;
     std::vector<int64_t> keys(cap, kDictEmpty);
     std::vector<int32_t> ranks(cap, -1);
+    int32_t sentinel_rank = -1;
     for (size_t r = 0; r < D; r++) {
         int64_t x = c->gdict[r];
-        if (x == kDictEmpty) continue;  // cannot be represented in the map; such rows are reported as overflow
+        if (x == kDictEmpty) {  // the free-slot marker itself: placed below, once every other key sits
+            sentinel_rank = (int32_t)r;
+            continue;
+        }
         uint32_t hh = host_dict_hash(x) & (cap - 1);
         while (keys[hh] != kDictEmpty) hh = (hh + 1) & (cap - 1);
         keys[hh] = x;
         ranks[hh] = (int32_t)r;
+    }
+    if (sentinel_rank >= 0) {
+        // A probe for INT64_MIN ends at the first free slot of ITS probe sequence, and there the lookups' `kx == x` holds
+        // before their free-slot test is reached (scan_generic.h: row_key, kernels.hip: k_rank_column): that slot carries the
+        // value's rank.  A probe for any other value that ends there fails `kx == x` and stops as at every free slot.
+        uint32_t hh = host_dict_hash(kDictEmpty) & (cap - 1);
+        while (keys[hh] != kDictEmpty) hh = (hh + 1) & (cap - 1);
+        ranks[hh] = sentinel_rank;
     }
     if (c->d_gdict_keys) SYBL_HIP(hipFree(c->d_gdict_keys));
     if (c->d_gdict_ranks) SYBL_HIP(hipFree(c->d_gdict_ranks));

@@ -4,7 +4,7 @@ merge of partial group tables.
 Reference: the only distributed mechanism in logv/sybil is `sybil aggregate` merging per-host gob
 results with CombineResults (node_aggregator.go:147-177, aggregate.go:414-467).  Here every rank
 holds an identically laid out integer table, so the merge is one SUM all-reduce (counts, sums,
-moments, buckets) and one MAX all-reduce (extrema, minima negated) over RCCL.  The functions take
+moments, buckets) and one MAX all-reduce (extrema, minima complemented) over RCCL.  The functions take
 any torch.distributed process group, so the protocol is exercised on CPU with gloo in
 tests/test_dist_gloo.py and on GPUs with the nccl(=RCCL) backend in bench.py.
 """
