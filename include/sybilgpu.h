@@ -528,6 +528,76 @@ const char *sybl_result_render(sybl_result *r, int format);
  * result is freed; bucket arrays are included for the rows that carry them. */
 const void *sybl_result_encode(sybl_result *r, int64_t *n_bytes);
 
+/* ------------------------------------------------------------------ samples
+ * `sybil query -samples` (cmd_query.go:330-343, table_query.go:96-228, printer.go:388-476): the ROWS behind a filter,
+ * newest first or ordered by an int column.  Filters are the aggregate path's (ANDed, strict, an unpopulated row fails);
+ * matching rows are selected and their values gathered on the GPU (csrc/samples.hip).
+ *
+ * The reference visits blocks one at a time and stops after the first block at which the matched count so far is STRICTLY
+ * greater than -limit, concatenates the visited blocks' Matched lists in Go map order (random), reverses or sorts, and
+ * truncates.  Restated deterministically, with block order for the map order (one of the orders the reference can produce):
+ *   blocks b = 0..B-1 in resident order; m_b = rows of block b that pass every filter;
+ *   blocks_visited P = the smallest p >= 1 with m_0 + .. + m_(p-1) > limit, or B if there is none;
+ *   candidates c_0 < c_1 < .. < c_(M-1) = the matching rows of blocks 0..P-1 in ascending row order; matched = M;
+ *   L = min(limit, M).
+ *   order_by NULL, "" or "$COUNT" (order_asc is ignored, as in the reference): c_(M-1), c_(M-2), .. -- the first L.
+ *   order_by = an INT column k: D = the candidates ordered by: rows without k first, then value descending; equal values,
+ *     and the rows without k among themselves, by descending row.  order_asc = 0: the first L of D; order_asc = 1: the
+ *     first L of D reversed (the reference reverses, then truncates).
+ *   order_by = a STR or SET column: SYBL_E_INVAL (the reference would compare block-local ids, record.go:60-73).
+ *   limit = 0: no rows; limit < 0: SYBL_E_INVAL; a table without blocks: no rows.
+ * Filters on more than 8 distinct columns are refused (SYBL_E_INVAL).
+ * Out of scope: -str-replace on samples; -encode-results of samples (gob interface{} values); the text form (PrintRecord
+ * prints a Go pointer dump); multi-rank merging -- the calls are rank-local and never collective, a host concatenates and
+ * truncates the ranks' rows as node_aggregator.go:59-79 does. */
+typedef struct {
+    int32_t n_filters;
+    const sybl_filter *filters;  /* as in sybl_query_desc */
+    int32_t n_columns;
+    const char *const *columns;  /* columns to return; NULL / 0 = every column (LoadAllColumns) */
+    const char *order_by;        /* NULL, "", "$COUNT", or an int column */
+    int32_t order_asc;
+    int32_t limit;               /* FLAGS.LIMIT; >= 0 */
+} sybl_samples_desc;
+
+typedef struct sybl_samples sybl_samples;
+
+/* Runs on the ctx stream and is complete on return.  The result owns everything it shows, strings included: it stays valid
+ * after sybl_table_free. */
+int sybl_table_samples(sybl_table *t, const sybl_samples_desc *d, sybl_samples **out);
+void sybl_samples_free(sybl_samples *s);
+
+typedef struct {
+    int64_t n_rows;          /* output rows (L) */
+    int64_t matched;         /* M */
+    int64_t blocks_visited;  /* P */
+    int64_t blocks_total;    /* B */
+    int64_t blocks_filtered; /* blocks the filter pass ran over (the visit proceeds in windows of blocks; 0 without filters) */
+    int32_t n_columns;
+    double filter_ms;        /* hipEvent time of the filter passes */
+    double select_ms;        /* hipEvent time of count, prefix, compaction, sort and gather */
+} sybl_samples_info;
+int sybl_samples_get_info(const sybl_samples *s, sybl_samples_info *out);
+
+/* One returned column over the n_rows output rows.  Only the arrays of the column's type are non-NULL. */
+typedef struct {
+    const char *name;
+    int32_t type;                    /* SYBL_INT_VAL | SYBL_STR_VAL | SYBL_SET_VAL */
+    const uint8_t *populated;        /* n_rows bytes 0/1 */
+    const int64_t *ints;             /* INT: n_rows values (0 where unpopulated) */
+    const int32_t *str_ids;          /* STR: the table-global dictionary ids (-1 where unpopulated) */
+    const char *const *strings;      /* STR: strings[i] = row i's string, NULL where unpopulated */
+    const int64_t *set_off;          /* SET: n_rows + 1 CSR offsets over the output rows */
+    const char *const *set_strings;  /* SET: the members' strings in stored order */
+} sybl_samples_col;
+int sybl_samples_column(const sybl_samples *s, int32_t i, sybl_samples_col *out);
+/* The table-wide logical row index of every output row (row 0 = the first row of the first block). */
+int sybl_samples_row_ids(const sybl_samples *s, const int64_t **logical_rows);
+/* -json: printJson([]*Sample) -- what encoding/json makes of the rows: "[]" when empty, else per row an object whose keys
+ * are the populated columns' names in bytewise sorted order; ints as decimals, strings escaped as encoding/json does (HTML
+ * escaping included), sets as arrays of strings.  Library-owned, valid until the result is freed. */
+const char *sybl_samples_render(sybl_samples *s);
+
 /* Test hook (no GPU needed): the library's regular-expression engine for re / nre str filters -- Go regexp
  * (RE2) syntax, unanchored search like regexp.MatchString (filter.go:213-236).  1 = match, 0 = no match,
  * -1 = the pattern does not compile (sybl_last_error says why). */

@@ -99,6 +99,25 @@ class RunStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class SamplesDesc(C.Structure):
+    _fields_ = [("n_filters", C.c_int32), ("filters", C.POINTER(Filter)), ("n_columns", C.c_int32),
+                ("columns", C.POINTER(C.c_char_p)), ("order_by", C.c_char_p), ("order_asc", C.c_int32), ("limit", C.c_int32)]
+
+
+class SamplesInfo(C.Structure):
+    _fields_ = [("n_rows", C.c_int64), ("matched", C.c_int64), ("blocks_visited", C.c_int64), ("blocks_total", C.c_int64),
+                ("blocks_filtered", C.c_int64), ("n_columns", C.c_int32), ("filter_ms", C.c_double), ("select_ms", C.c_double)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class SamplesCol(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("type", C.c_int32), ("populated", C.POINTER(C.c_uint8)), ("ints", C.POINTER(C.c_int64)),
+                ("str_ids", C.POINTER(C.c_int32)), ("strings", C.POINTER(C.c_char_p)), ("set_off", C.POINTER(C.c_int64)),
+                ("set_strings", C.POINTER(C.c_char_p))]
+
+
 # every symbol include/sybilgpu.h declares: (restype, argtypes)
 P = C.c_void_p
 SIGNATURES = {
@@ -171,6 +190,12 @@ SIGNATURES = {
     "sybl_debug_query_cells": (C.c_int, [P, C.c_int, C.c_int, P, C.c_int64, C.POINTER(C.c_int64)]),
     "sybl_result_render": (C.c_char_p, [P, C.c_int]),
     "sybl_result_encode": (C.c_void_p, [P, C.POINTER(C.c_int64)]),
+    "sybl_table_samples": (C.c_int, [P, C.POINTER(SamplesDesc), C.POINTER(P)]),
+    "sybl_samples_free": (None, [P]),
+    "sybl_samples_get_info": (C.c_int, [P, C.POINTER(SamplesInfo)]),
+    "sybl_samples_column": (C.c_int, [P, C.c_int32, C.POINTER(SamplesCol)]),
+    "sybl_samples_row_ids": (C.c_int, [P, C.POINTER(C.POINTER(C.c_int64))]),
+    "sybl_samples_render": (C.c_char_p, [P]),
 }
 
 _lib = None

@@ -538,6 +538,10 @@ struct Query {
 };
 
 int plan_query(Table *t, const sybl_query_desc *d, Query *q);  // planner.cpp
+int plan_filter_slots(Table *t, const sybl_filter *filters, int n_filters, Query *q);  // planner.cpp: the filters alone, for samples.hip
+void deal_tiles(const std::vector<Segment> &runs, int n_wg, std::vector<Segment> &segs, std::vector<int32_t> &wg_seg_begin);  // planner.cpp
+void json_escape(const std::string &s, std::string &o);  // render.cpp: a string as encoding/json writes it
+int samples_run(Table *t, const sybl_samples_desc *d, sybl_samples **out);  // samples.hip
 int query_rescan_without_part_hist(Query *q);
 
 constexpr int kMaxScatterRanks = 64;  // the SUM section is padded so that a reduce-scatter over up to this many ranks fits in place

@@ -647,6 +647,37 @@ static int select_part_hist(Table *t, Query *q, const std::vector<int> &slot_col
     return SYBL_OK;
 }
 
+// Runs of physical rows -> an equal share of tiles per workgroup: segs[wg_seg_begin[w] .. wg_seg_begin[w + 1]) are workgroup
+// w's.  (Planner::work for a whole query; csrc/samples.hip for each window of blocks a samples query visits.)
+void deal_tiles(const std::vector<Segment> &runs, int n_wg, std::vector<Segment> &segs, std::vector<int32_t> &wg_seg_begin) {
+    int64_t total_tiles = 0;
+    for (auto &r : runs) total_tiles += (r.n + kTileRows - 1) / kTileRows;
+    segs.clear();
+    wg_seg_begin.assign((size_t)n_wg + 1, 0);
+    size_t ri = 0;
+    int64_t tile_in_run = 0;  // tiles of runs[ri] already handed out
+    for (int w = 0; w < n_wg; w++) {
+        wg_seg_begin[(size_t)w] = (int32_t)segs.size();
+        int64_t want = total_tiles * (w + 1) / n_wg - total_tiles * w / n_wg;
+        while (want > 0 && ri < runs.size()) {
+            int64_t run_tiles = (runs[ri].n + kTileRows - 1) / kTileRows;
+            int64_t take = std::min(want, run_tiles - tile_in_run);
+            Segment sg;
+            sg.start = runs[ri].start + tile_in_run * kTileRows;
+            int64_t end = std::min(runs[ri].start + runs[ri].n, sg.start + take * kTileRows);
+            sg.n = end - sg.start;
+            segs.push_back(sg);
+            tile_in_run += take;
+            want -= take;
+            if (tile_in_run == run_tiles) {
+                ri++;
+                tile_in_run = 0;
+            }
+        }
+    }
+    wg_seg_begin[(size_t)n_wg] = (int32_t)segs.size();
+}
+
 // The planner: sybl_query_desc + table statistics -> ScanPlan (+ FastPlan / EmitPlan), work list and
 // device buffers.  One method per step, in the order the reference builds a query
 // (cmd_query.go:204-333: filters, groupings, aggregations, time / weight options).
@@ -1497,34 +1528,7 @@ struct Planner {
                 runs.push_back(blk);
             }
         }
-        int64_t total_tiles = 0;
-        for (auto &r : runs) total_tiles += (r.n + kTileRows - 1) / kTileRows;
-        q->segs.clear();
-        q->wg_seg_begin.assign((size_t)q->n_wg + 1, 0);
-        {
-            size_t ri = 0;
-            int64_t tile_in_run = 0;  // tiles of runs[ri] already handed out
-            for (int w = 0; w < q->n_wg; w++) {
-                q->wg_seg_begin[(size_t)w] = (int32_t)q->segs.size();
-                int64_t want = total_tiles * (w + 1) / q->n_wg - total_tiles * w / q->n_wg;
-                while (want > 0 && ri < runs.size()) {
-                    int64_t run_tiles = (runs[ri].n + kTileRows - 1) / kTileRows;
-                    int64_t take = std::min(want, run_tiles - tile_in_run);
-                    Segment sg;
-                    sg.start = runs[ri].start + tile_in_run * kTileRows;
-                    int64_t end = std::min(runs[ri].start + runs[ri].n, sg.start + take * kTileRows);
-                    sg.n = end - sg.start;
-                    q->segs.push_back(sg);
-                    tile_in_run += take;
-                    want -= take;
-                    if (tile_in_run == run_tiles) {
-                        ri++;
-                        tile_in_run = 0;
-                    }
-                }
-            }
-            q->wg_seg_begin[(size_t)q->n_wg] = (int32_t)q->segs.size();
-        }
+        deal_tiles(runs, q->n_wg, q->segs, q->wg_seg_begin);
         return SYBL_OK;
     }
 
@@ -1894,6 +1898,33 @@ struct Planner {
 int plan_query(Table *t, const sybl_query_desc *d, Query *q) {
     Planner p(t, d, q);
     return p.run();
+}
+
+// The filters of a samples query (csrc/samples.hip), lowered exactly as a query's are: the planner's own steps up to the
+// finished slots, and nothing behind them.  q->plan then holds one filter-only slot per distinct filter column -- what
+// k_prefilter evaluates (Planner::prefilter builds the same kind of plan) --, q->never_matches and q->d_idmasks are set;
+// the caller points plan.segs / plan.wg_seg_begin at its work and uploads the plan.
+int plan_filter_slots(Table *t, const sybl_filter *filters, int n_filters, Query *q) {
+    sybl_query_desc d;
+    memset(&d, 0, sizeof(d));
+    d.n_filters = n_filters;
+    d.filters = filters;
+    Planner p(t, &d, q);
+    int rc;
+    if ((rc = p.setup())) return rc;
+    if ((rc = p.filters())) return rc;
+    if (p.slot_col.empty()) {  // (no filter: finish_slots would pick a column to drive a scan)
+        q->plan.n_slots = 0;
+        return SYBL_OK;
+    }
+    if ((rc = p.finish_slots())) return rc;
+    for (int s = 0; s < q->plan.n_slots; s++) {
+        SlotDesc &sd = q->plan.slot[s];
+        sd.gmissing = -1;
+        sd.gmissing64 = -1;
+        sd.agg_index = -1;
+    }
+    return SYBL_OK;
 }
 
 }  // namespace sybl

@@ -15,7 +15,7 @@ namespace sybl {
 
 // ------------------------------------------------------------------ rendering (printer.go)
 
-static void json_escape(const std::string &s, std::string &o) {
+void json_escape(const std::string &s, std::string &o) {
     o += '"';
     for (unsigned char ch : s) {
         switch (ch) {

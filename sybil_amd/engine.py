@@ -251,14 +251,8 @@ class Table:
     def SetFilter(col, op, value):
         return (col, op, str(value))
 
-    def query(self, filters=(), groups=(), aggs=(), op="avg", hist_bucket=0, want_percentiles=True, time_col=None,
-              time_bucket=0, weight_col=None, order_by="$COUNT", order_asc=False, limit=0, block_skip=False, loghist=False, str_replace=(),
-              distincts=(), printed_only=False):
-        """str_replace: [(col, pattern, replacement)] or [(col, [replaced string per dictionary id])] (-str-replace).
-        distincts: columns of a count-distinct query (-distinct): rows then carry "distinct" (Result.distinct()).
-        printed_only: the caller is a printer (sybl_query_desc.printed_only): with limit > 0 and many histogram groups only the
-        first `limit` rows of the sort order and Cumulative carry percentiles / stddev / bucket arrays."""
-        keep = []
+    @staticmethod
+    def _filter_array(filters, keep):
         farr = (N.Filter * max(len(filters), 1))()
         for i, f in enumerate(filters):
             col, opn, val = f[0], f[1], f[2]
@@ -275,6 +269,36 @@ class Table:
                 ff.id_match = m.ctypes.data
                 ff.id_match_len = m.size
             farr[i] = ff
+        return farr
+
+    def samples(self, filters=(), columns=None, order_by="$COUNT", order_asc=False, limit=100):
+        """`sybil query -samples` (sybl_table_samples): the rows behind the filters, newest first or ordered by an int
+        column.  columns=None returns every column.  Everything is copied out of the library; the handle is freed."""
+        keep = []
+        d = N.SamplesDesc()
+        d.n_filters, d.filters = len(filters), C.cast(self._filter_array(filters, keep), C.POINTER(N.Filter))
+        names = [_b(c) for c in columns] if columns is not None else []
+        carr = (C.c_char_p * max(len(names), 1))(*names)
+        d.n_columns, d.columns = len(names), (C.cast(carr, C.POINTER(C.c_char_p)) if names else None)
+        d.order_by = _b(order_by) if order_by else None
+        d.order_asc = 1 if order_asc else 0
+        d.limit = limit
+        h = C.c_void_p()
+        N.check(N.lib().sybl_table_samples(self._h, C.byref(d), C.byref(h)))
+        try:
+            return Samples(h)
+        finally:
+            N.lib().sybl_samples_free(h)
+
+    def query(self, filters=(), groups=(), aggs=(), op="avg", hist_bucket=0, want_percentiles=True, time_col=None,
+              time_bucket=0, weight_col=None, order_by="$COUNT", order_asc=False, limit=0, block_skip=False, loghist=False, str_replace=(),
+              distincts=(), printed_only=False):
+        """str_replace: [(col, pattern, replacement)] or [(col, [replaced string per dictionary id])] (-str-replace).
+        distincts: columns of a count-distinct query (-distinct): rows then carry "distinct" (Result.distinct()).
+        printed_only: the caller is a printer (sybl_query_desc.printed_only): with limit > 0 and many histogram groups only the
+        first `limit` rows of the sort order and Cumulative carry percentiles / stddev / bucket arrays."""
+        keep = []
+        farr = self._filter_array(filters, keep)
         g = [_b(x) for x in groups]
         a = [_b(x) for x in aggs]
         garr = (C.c_char_p * max(len(g), 1))(*g)
@@ -315,6 +339,50 @@ class Table:
         qy = Query(self, h, list(groups), list(aggs))
         qy.n_distincts = len(dn)
         return qy
+
+
+class Samples:
+    """A samples result, copied out of the library: `rows` (a list of dicts shaped like the reference's toSample: int, str,
+    list of str; an unpopulated column is absent), `row_ids` (table-wide logical row per output row), `info`, `json()`."""
+
+    def __init__(self, handle):
+        L = N.lib()
+        info = N.SamplesInfo()
+        N.check(L.sybl_samples_get_info(handle, C.byref(info)))
+        self.info = info.as_dict()
+        n = info.n_rows
+        ids = C.POINTER(C.c_int64)()
+        N.check(L.sybl_samples_row_ids(handle, C.byref(ids)))
+        self.row_ids = np.ctypeslib.as_array(ids, shape=(n,)).copy() if n else np.zeros(0, dtype=np.int64)
+        self.rows = [{} for _ in range(n)]
+        self.columns = []
+        for c in range(info.n_columns):
+            col = N.SamplesCol()
+            N.check(L.sybl_samples_column(handle, c, C.byref(col)))
+            name = col.name.decode("utf-8", "replace")
+            self.columns.append(name)
+            if not n:
+                continue
+            pop = np.ctypeslib.as_array(col.populated, shape=(n,))
+            if col.type == N.INT_VAL:
+                ints = np.ctypeslib.as_array(col.ints, shape=(n,)).tolist()
+                for i in np.nonzero(pop)[0].tolist():
+                    self.rows[i][name] = ints[i]
+            elif col.type == N.STR_VAL:
+                for i in np.nonzero(pop)[0].tolist():
+                    self.rows[i][name] = col.strings[i].decode("utf-8", "replace")
+            else:
+                off = np.ctypeslib.as_array(col.set_off, shape=(n + 1,)).tolist()
+                for i in np.nonzero(pop)[0].tolist():
+                    self.rows[i][name] = [col.set_strings[k].decode("utf-8", "replace") for k in range(off[i], off[i + 1])]
+        s = L.sybl_samples_render(handle)
+        if s is None:
+            raise N.SyblError(N.E_INVAL, (L.sybl_last_error() or b"").decode())
+        self._json = s.decode("utf-8", "replace")
+
+    def json(self):
+        """-json: the bytes printJson([]*Sample) writes."""
+        return self._json
 
 
 class Query:
