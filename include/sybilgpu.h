@@ -290,7 +290,8 @@ typedef struct {
     int32_t want_percentiles;
     const char *time_col;       /* with time_bucket > 0: time-series query */
     int64_t time_bucket;        /* QuerySpec.TimeBucket */
-    const char *weight_col;     /* OPTS.WEIGHT_COL */
+    const char *weight_col;     /* OPTS.WEIGHT_COL.  Weights below 1 are not supported: the reference indexes out of range once a
+                                 * running count turns negative, and the bounds that recover avg and stddev assume Count > 0 */
     const char *order_by;       /* "$COUNT", an aggregated column, or NULL/"" = unsorted */
     int32_t order_asc;
     int32_t limit;              /* FLAGS.LIMIT; <= 0 = all groups */
@@ -426,7 +427,10 @@ typedef struct {
                            * count n and the bounds [lo, hi] of the accepted values while n*(hi - lo) < 2^64 (the group's own
                            * extrema where they are tracked, then (n-2)*(hi - lo); else the column's); beyond that -- four rows
                            * of 9e18 next to one of -4e18 -- avg, stddev and the printed sum come from the wrapped sum */
-    double stddev;        /* GetStdDev semantics (hist_basic.go:192-219); 0 in AVG mode */
+    double stddev;        /* GetStdDev semantics (hist_basic.go:192-219); 0 in AVG mode.  Where it comes from the bucket moments
+                           * sb = sum(b*w) and sb2 = sum(b*b*w) (no percentiles wanted, or 2048+ groups), each kept mod 2^64, the true
+                           * sb2 is recovered from its low bits, sb and Count while (n_values-1)*sb - sb*sb/Count < 2^64 (always
+                           * when (n_values-1)^2 * Count < 2^64: any Count below 1.8e13); beyond that stddev comes from the wrapped sb2 */
     int64_t min, max;     /* BasicHist.Min/Max incl. the reference's initial values */
     int64_t bucket_size;  /* HIST: BasicHist.BucketSize */
     int64_t num_buckets;  /* HIST: BasicHist.NumBuckets */

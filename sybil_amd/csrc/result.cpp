@@ -76,6 +76,43 @@ static __int128 true_sum(const AggInfo &ai, const AggAcc &a, int64_t cnt) {
     return true_sum(ai, a.sum, cnt, ai.d.m_max >= 0, a.vmax, ai.d.m_nmin >= 0, a.nmin);
 }
 
+// The true bucket moments sb = sum(b*w) and sb2 = sum(b*b*w) of a cell from the 64 bits the scan bodies and k_hist_summary keep
+// of each (with a weight column sb2 passes 2^63 once the weighted Count of the top buckets passes 9.2e12).  Every reader goes
+// through here: agg_finish (the moments form of GetStdDev) and the sums of Cumulative.
+//
+// The n = Count units of weight each sit in a bucket of [0, top], top = n_values - 1 (outliers are clamped into it), so sb lies
+// in [0, top*n] and -- Cauchy-Schwarz below, b <= top above -- sb2 in [sb^2/n, top*sb]; while a range is narrower than 2^64 the
+// true value is the one member of it with the stored low bits.  top^2*n < 2^64 puts both below 2^64 outright (no division:
+// every unweighted query).  Beyond the bound (and for weights below 1) the wrapped values are all there is: the limit
+// DESIGN.md and include/sybilgpu.h state.
+struct Moments {
+    __int128 sb, sb2;
+};
+
+static Moments true_moments(int64_t n_values, int64_t sb, int64_t sb2, int64_t n) {
+    Moments m = {(__int128)sb, (__int128)sb2};
+    if (n <= 0 || n_values < 1) return m;
+    const unsigned __int128 top = (unsigned __int128)(n_values - 1), sb_max = top * (unsigned __int128)n;
+    if (sb_max >> 64) return m;
+    const unsigned __int128 B = (uint64_t)sb;
+    if (B > sb_max) return m;  // (the bounds do not describe this cell)
+    m.sb = (__int128)B;
+    if (!((top * sb_max) >> 64)) {
+        m.sb2 = (__int128)(unsigned __int128)(uint64_t)sb2;
+        return m;
+    }
+    const unsigned __int128 lo = B * B / (unsigned __int128)n, hi = top * B;  // (B < 2^64: neither product leaves 128 bits)
+    if (hi < lo || ((hi - lo) >> 64)) return m;
+    const unsigned __int128 off = (uint64_t)((uint64_t)sb2 - (uint64_t)lo);
+    if (off <= hi - lo) m.sb2 = (__int128)(lo + off);
+    return m;
+}
+
+static Moments true_moments(const AggInfo &ai, const AggAcc &a, int64_t cnt) {
+    if (a.wide_mom) return {a.wide_sb, a.wide_sb2};
+    return true_moments(ai.d.n_values, a.sb, a.sb2, cnt);
+}
+
 // (Q: what the row builders read of the query -- op, weighted, loghist, want_percentiles, aggs: FinCtx, the result's own copy)
 template <class Q>
 static void agg_finish(const Q *q, Result *R, const AggInfo &ai, const AggAcc &a, int64_t row_count, sybl_agg_out &o,
@@ -199,7 +236,8 @@ static void agg_finish(const Q *q, Result *R, const AggInfo &ai, const AggAcc &a
     } else {
         // moments form of the same sum: e_b - avg = BS*b + (hmin - avg)
         long double BS = (long double)A.bucket_size, c = (long double)A.hmin - (long double)o.avg;
-        long double var = cnt != 0 ? (BS * BS * (long double)a.sb2 + 2.0L * BS * c * (long double)a.sb + c * c * (long double)cnt) /
+        const Moments mom = true_moments(ai, a, cnt);
+        long double var = cnt != 0 ? (BS * BS * (long double)mom.sb2 + 2.0L * BS * c * (long double)mom.sb + c * c * (long double)cnt) /
                                          (long double)cnt
                                    : 0.0L;
         var += out_term;
@@ -1209,6 +1247,10 @@ void result_ensure_rows(Result *R) {
                     d.wide = true;
                     d.sb += s.sb;
                     d.sb2 += s.sb2;
+                    const Moments mom = true_moments(C.aggs[a], s, s.cnt);
+                    d.wide_sb += mom.sb;
+                    d.wide_sb2 += mom.sb2;
+                    d.wide_mom = true;
                     d.n_out += s.n_out;
                     d.sum_out += s.sum_out;
                     for (int k = 0; k < 4; k++) d.sq[k] += s.sq[k];
@@ -1266,6 +1308,9 @@ void result_ensure_rows(Result *R) {
                 d.wide = d.wide || s2.wide;
                 d.sb += s2.sb;
                 d.sb2 += s2.sb2;
+                d.wide_sb += s2.wide_sb;
+                d.wide_sb2 += s2.wide_sb2;
+                d.wide_mom = d.wide_mom || s2.wide_mom;
                 d.n_out += s2.n_out;
                 d.sum_out += s2.sum_out;
                 for (int j = 0; j < 4; j++) d.sq[j] += s2.sq[j];

@@ -19,7 +19,10 @@ struct AggAcc {
     // Cumulative only: the cells' true sums added up in 128 bits (true_sum in result.cpp); `sum` stays their low 64 bits
     bool wide = false;
     __int128 wide_sum = 0;
-    int64_t sb = 0, sb2 = 0;
+    int64_t sb = 0, sb2 = 0;  // the low 64 bits of the bucket moments sum(b*w), sum(b*b*w)
+    // Cumulative only: the cells' true moments added up in 128 bits (true_moments in result.cpp)
+    bool wide_mom = false;
+    __int128 wide_sb = 0, wide_sb2 = 0;
     int64_t n_out = 0;
     uint64_t sum_out = 0;
     uint64_t sq[4] = {0, 0, 0, 0};
