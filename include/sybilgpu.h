@@ -602,6 +602,48 @@ int sybl_samples_row_ids(const sybl_samples *s, const int64_t **logical_rows);
  * escaping included), sets as arrays of strings.  Library-owned, valid until the result is freed. */
 const char *sybl_samples_render(sybl_samples *s);
 
+/* ------------------------------------------------------------------ digest
+ * The reference's write path sorts the records by Timestamp before it cuts them into blocks (SaveRecordsToColumns,
+ * table_io.go:119-130; saveRecordList, table_io.go:80-117; Timestamp = the time column's value, Go's zero for a row without
+ * one: column_store.go:9-20, column_store_io.go:741-743,768-770).  sybl_table_digest is that step for a resident table: the
+ * table's rows in time order, cut into blocks, as a NEW resident table.  Key extraction, the sort and the gather of every
+ * column run on the GPU (csrc/digest.hip).  Restated deterministically:
+ *   source rows: the logical rows of the live blocks in resident order, r = 0..N-1.  Blocks without rows (left behind by
+ *     sybl_table_refresh) and the padding between blocks contribute nothing.
+ *   key k(r) = the value of time_col in row r if it is populated, else 0; keys compare as signed int64.
+ *   order: ascending k, STABLE -- equal keys keep source order.  (sort.Sort in the reference is unstable; the stable order is
+ *     one of the orders it can produce, and the one defined here.)
+ *   time_col: NULL or "" = "time" (the default of FLAGS.TIME_COL).  A name the table does not hold, or a column that is not
+ *     an INT column: SYBL_E_INVAL.  (The reference would sort on all-zero keys for an unknown name; this call refuses.)
+ *   block_rows: 0 = 65536 (CHUNK_SIZE, table.go:44); 1..65536 as given; anything else: SYBL_E_INVAL.
+ *   output block j holds sorted rows [j * block_rows, min(N, (j+1) * block_rows)).  N = 0: the columns and no blocks.
+ * The output table: same ctx, same name, the same columns in the same order with their type and IntInfo; the str / set
+ * dictionaries copied id for id (an id means the same string in both tables); declared bounds (sybl_table_set_bounds) and
+ * has_missing copied; compact storage iff the source is in compact mode (every output value is a source value: the source
+ * columns' widths and bases are kept).  It is not attached to a directory.  Group dictionaries and derived columns are not
+ * copied: the next prepare builds them as for any table.  Per-block min / max / populated counts are exact for the new
+ * blocks; table-wide extrema may be the source's (bounds of a superset are bounds).
+ * The source table is untouched and its version does not move: prepared queries on it stay valid.  The output owns
+ * everything it shows and outlives the source; free it with sybl_table_free.
+ * Rank-local, never collective; runs on the ctx stream and is complete on return.  N >= 2^31 rows: SYBL_E_INVAL (the sort
+ * counts its items in an int); so are more than 2^32 - 1 physical rows in the source, dead blocks included (source rows
+ * travel as 32-bit numbers).  The call needs the table's size again plus, per row, two keys (4 bytes each when the
+ * time column's range -- with 0 in it, if a row lacks the column -- fits 32 bits, else 8), two 4-byte row numbers and the sort's scratch; when
+ * HBM runs out it returns SYBL_E_NOMEM, frees everything it allocated and leaves *out NULL. */
+int sybl_table_digest(sybl_table *t, const char *time_col, int32_t block_rows, sybl_table **out);
+
+/* Where the device time of the sybl_table_digest that made this table went (zeros for any other table), and the bytes each
+ * phase moves, computed from the shapes. */
+typedef struct {
+    int64_t rows, blocks;  /* N, output blocks */
+    int32_t key_bits;      /* bits of the key the sort ordered by */
+    double keys_ms;        /* hipEvent time: key extraction */
+    double sort_ms;        /* ... the radix sort */
+    double gather_ms;      /* ... gather of every column, validity words and block statistics */
+    int64_t keys_bytes, sort_bytes, gather_bytes;
+} sybl_digest_stats;
+int sybl_table_digest_stats(const sybl_table *t, sybl_digest_stats *out);
+
 /* Test hook (no GPU needed): the library's regular-expression engine for re / nre str filters -- Go regexp
  * (RE2) syntax, unanchored search like regexp.MatchString (filter.go:213-236).  1 = match, 0 = no match,
  * -1 = the pattern does not compile (sybl_last_error says why). */

@@ -118,6 +118,15 @@ class SamplesCol(C.Structure):
                 ("set_strings", C.POINTER(C.c_char_p))]
 
 
+class DigestStats(C.Structure):
+    _fields_ = [("rows", C.c_int64), ("blocks", C.c_int64), ("key_bits", C.c_int32), ("keys_ms", C.c_double),
+                ("sort_ms", C.c_double), ("gather_ms", C.c_double), ("keys_bytes", C.c_int64), ("sort_bytes", C.c_int64),
+                ("gather_bytes", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol include/sybilgpu.h declares: (restype, argtypes)
 P = C.c_void_p
 SIGNATURES = {
@@ -196,6 +205,8 @@ SIGNATURES = {
     "sybl_samples_column": (C.c_int, [P, C.c_int32, C.POINTER(SamplesCol)]),
     "sybl_samples_row_ids": (C.c_int, [P, C.POINTER(C.POINTER(C.c_int64))]),
     "sybl_samples_render": (C.c_char_p, [P]),
+    "sybl_table_digest": (C.c_int, [P, C.c_char_p, C.c_int32, C.POINTER(P)]),
+    "sybl_table_digest_stats": (C.c_int, [P, C.POINTER(DigestStats)]),
 }
 
 _lib = None

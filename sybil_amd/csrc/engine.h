@@ -204,6 +204,7 @@ struct Table {
     int64_t version = 0;        // bumped by every change a prepared query would not know about
     int64_t broken_blocks = 0;  // blocks the loader skipped (unreadable info / column unpack error)
     sybl_load_stats load_stats{};  // of the sybl_table_open / sybl_table_refresh that last loaded blocks
+    sybl_digest_stats digest_stats{};  // of the sybl_table_digest that made this table (digest.hip)
     std::string src_dir;           // <dir>/<table> the table was opened from ("" = built through the ABI)
     int src_rank = 0, src_nranks = 1;
     std::vector<LoadedBlock> loaded;
@@ -542,6 +543,7 @@ int plan_filter_slots(Table *t, const sybl_filter *filters, int n_filters, Query
 void deal_tiles(const std::vector<Segment> &runs, int n_wg, std::vector<Segment> &segs, std::vector<int32_t> &wg_seg_begin);  // planner.cpp
 void json_escape(const std::string &s, std::string &o);  // render.cpp: a string as encoding/json writes it
 int samples_run(Table *t, const sybl_samples_desc *d, sybl_samples **out);  // samples.hip
+int digest_run(Table *t, const char *time_col, int32_t block_rows, sybl_table **out);  // digest.hip
 int query_rescan_without_part_hist(Query *q);
 
 constexpr int kMaxScatterRanks = 64;  // the SUM section is padded so that a reduce-scatter over up to this many ranks fits in place

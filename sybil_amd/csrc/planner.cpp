@@ -1617,8 +1617,8 @@ struct Planner {
         int rc;
         // ---- LDS-window strategy: a time-series table too large for LDS, scanned by workgroups whose
         // contiguous rows each span only a few time buckets (tables are digested in time order,
-        // table_io.go:119-122 sorts by Timestamp).  Exact per-block extrema of the time column give
-        // every workgroup its window.
+        // table_io.go:119-122 sorts by Timestamp, or made so by sybl_table_digest).  Exact per-block
+        // extrema of the time column give every workgroup its window.
         P.windowed = 0;
         P.lds_cells = (int32_t)n_cells;
         P.wg_cell_base = nullptr;

@@ -215,6 +215,19 @@ class Table:
         """Write the table under directory/<name>/ in the reference's on-disk format (sybl_table_save)."""
         N.check(N.lib().sybl_table_save(self._h, _b(directory)))
 
+    def digest(self, time_col="time", block_rows=0):
+        """The table's rows in time order (stable; a row without time_col sorts as 0), cut into blocks of block_rows
+        (0 = 65536), as a NEW resident table (sybl_table_digest).  This table is untouched; free both."""
+        h = C.c_void_p()
+        N.check(N.lib().sybl_table_digest(self._h, _b(time_col) if time_col is not None else None, block_rows, C.byref(h)))
+        return Table(self.ctx, h, self.name)
+
+    def digest_stats(self):
+        """Device time and bytes of the phases of the digest() that made this table (sybl_table_digest_stats)."""
+        st = N.DigestStats()
+        N.check(N.lib().sybl_table_digest_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
     def refresh(self):
         """Follow the directory the table was opened from (sybl_table_refresh): returns (added, dropped, reloaded) blocks."""
         a, d, r = C.c_int64(0), C.c_int64(0), C.c_int64(0)
