@@ -1532,6 +1532,18 @@ struct Planner {
         return SYBL_OK;
     }
 
+    // the most rows one lane of k_scan_packed sees: four of every tile of its workgroup
+    int64_t max_lane_rows() const {
+        int64_t lane_rows = 0;
+        for (int w = 0; w < q->n_wg; w++) {
+            int64_t mine = 0;
+            for (int32_t si = q->wg_seg_begin[(size_t)w]; si < q->wg_seg_begin[(size_t)w + 1]; si++)
+                mine += (q->segs[(size_t)si].n + kPackedTileRows - 1) / kPackedTileRows * kPackedRows;
+            lane_rows = std::max(lane_rows, mine);
+        }
+        return lane_rows;
+    }
+
     // FastPlan::cshift (scan_fast.h): in avg mode over compact storage, with every value populated, Result.Count shares an LDS
     // word with aggregation 0's sum of stored offsets.  A word belongs to one (cell, replica): it takes the rows of the
     // 1024 >> rep_shift lanes of that replica, each of which sees four rows of every tile of its workgroup -- that many rows, and
@@ -1541,13 +1553,7 @@ struct Planner {
         FP.cshift = 0;
         if (!q->fast || !q->fast_packed || q->fast_packed_n || q->part_hist || FP.nul || q->fast_na < 1 || env("SYBL_NO_CPACK")) return;
         if (q->fast_mode != kFastAvg && q->fast_mode != kFastAvgMax) return;
-        int64_t lane_rows = 0;
-        for (int w = 0; w < q->n_wg; w++) {
-            int64_t mine = 0;
-            for (int32_t si = q->wg_seg_begin[(size_t)w]; si < q->wg_seg_begin[(size_t)w + 1]; si++)
-                mine += (q->segs[(size_t)si].n + kPackedTileRows - 1) / kPackedTileRows * kPackedRows;
-            lane_rows = std::max(lane_rows, mine);
-        }
+        const int64_t lane_rows = max_lane_rows();
         const unsigned __int128 slot_rows = (unsigned __int128)std::max<int64_t>(lane_rows, 1) * (unsigned __int128)(kWgThreads >> P.rep_shift);
         const Column *c = t->cols[(size_t)q->aggs[0].col].get();
         // (the stored offsets of the resident rows: exact extrema minus the storage base, never above what the width holds)
@@ -1563,6 +1569,91 @@ struct Planner {
         // SYBL_PLAN_TRACE=1 (diagnostic): the decision and the widths behind it, also when they do not fit (cshift=0)
         if (env("SYBL_PLAN_TRACE"))
             fprintf(stderr, "count packing: cshift=%d sum_bits=%d count_bits=%d slot_rows=%lld\n", (int)FP.cshift, sum_bits, count_bits, (long long)slot_rows);
+    }
+
+    // FastPlan::lean (scan_fast.h): what k_scan_packed's plain kernels may assume about the resident rows, proved from the
+    // columns' EXACT extrema (never the declared bounds; a table that grows re-plans its queries, as for cshift).
+    //  * kLeanProved (moments and full-histogram modes): every group digit lies inside [0, gcard) -- the table is not windowed,
+    //    so it covers every cell --, and every bucket numerator value - h.Min and every bucket size is below 2^24;
+    //  * kLeanMoments (moments mode): the lean words hold what a (cell, replica) can receive.  The layout's word count decides
+    //    the replica count, that decides the rows per replica, and those decide whether the layout fits; when it does not, the
+    //    plan keeps the layout AND the replica count it had.
+    // SYBL_NO_LEAN=1: neither.  SYBL_PLAN_TRACE=1: the decision and the widths behind it.
+    void plan_lean() {
+        FastPlan &FP = q->fplan;
+        FP.lean = 0;
+        FP.lds_sum_fields = 0;
+        if (!q->fast || !q->fast_packed || q->fast_packed_n || q->part_hist || FP.nul || q->fast_na < 1 || env("SYBL_NO_LEAN")) return;
+        if (q->fast_mode != kFastMoments && q->fast_mode != kFastHist) return;
+        const int na = q->fast_na;
+        // -- kLeanProved
+        bool digits = !P.windowed, mul24 = true;
+        for (size_t g = 0; g < q->groups.size() && digits; g++) {
+            const int ci = q->groups[g].col;
+            const Column *c = ci >= 0 ? t->cols[(size_t)ci].get() : nullptr;
+            // (digits that are ranks of a dictionary are not value - gmin: no proof)
+            if (!c || c->type != SYBL_INT_VAL || c->n_pop <= 0 || q->groups[g].dict || q->groups[g].rank) {
+                digits = false;
+                break;
+            }
+            const __int128 lo = (__int128)c->exact_min - (__int128)FP.gmin[g], hi = (__int128)c->exact_max - (__int128)FP.gmin[g];
+            digits = lo >= 0 && hi < (__int128)FP.gcard[g];
+        }
+        for (int a = 0; a < na; a++) {
+            const Column *c = t->cols[(size_t)q->aggs[(size_t)a].col].get();
+            if (FP.bucket_size[a] >= (1u << 24)) mul24 = false;
+            if (c->n_pop > 0) {
+                const __int128 lo = (__int128)c->exact_min - (__int128)FP.hmin[a], hi = (__int128)c->exact_max - (__int128)FP.hmin[a];
+                if (lo < 0 || hi >= ((__int128)1 << 24)) mul24 = false;
+            }
+        }
+        if (digits && mul24) FP.lean |= (int32_t)kLeanProved;
+        if (q->fast_mode != kFastMoments) {
+            if (env("SYBL_PLAN_TRACE")) fprintf(stderr, "lean hist: proved=%d digits=%d mul24=%d\n", (FP.lean & (int32_t)kLeanProved) ? 1 : 0, (int)digits, (int)mul24);
+            return;
+        }
+        // -- kLeanMoments
+        const int words_now = P.n_sum_fields, words_lean = lean_sum_fields(na);
+        bool shape = P.n_max_fields == 0 && P.n_sum_fields == 1 + 3 * na && FP.f_samples < 0 && FP.hist_lds == 0;
+        for (int a = 0; a < na; a++) shape = shape && FP.f_sum[a] > 0 && FP.f_sb[a] > 0 && FP.f_sb2[a] > 0 && FP.f_cnt[a] < 0 && FP.f_pop[a] < 0 && FP.f_out[a] < 0;
+        int rs = 0, cshift = 0;
+        unsigned __int128 slot_rows = 0;
+        uint64_t umax[kFastMaxA] = {0}, bmax[kFastMaxA] = {0};
+        if (shape) {
+            // (the replicas the lean table affords: the budgets strategy() and window() use)
+            int64_t budget = kLdsBudgetBytes;
+            if (!P.windowed)
+                if (const char *e = env("SYBL_REP_BUDGET_KB")) budget = std::min<int64_t>(kLdsBudgetBytes, std::max<int64_t>(1, atoll(e)) * 1024);
+            const int64_t bytes = (int64_t)words_lean * P.lds_cells * 8;
+            while (rs < 6 && (bytes << (rs + 1)) <= budget) rs++;
+            slot_rows = (unsigned __int128)std::max<int64_t>(max_lane_rows(), 1) * (unsigned __int128)(kWgThreads >> rs);
+            for (int a = 0; a < na; a++) {
+                const Column *c = t->cols[(size_t)q->aggs[(size_t)a].col].get();
+                // (the stored offsets of the resident rows: exact extrema minus the storage base, never above what the width holds)
+                unsigned __int128 u = c->elem >= 4 ? 0xFFFFFFFFull : c->elem == 2 ? 0xFFFFull : 0xFFull;
+                if (c->n_pop > 0 && c->exact_max >= c->vbase) u = std::min<unsigned __int128>(u, (unsigned __int128)((__int128)c->exact_max - (__int128)c->vbase));
+                umax[a] = (uint64_t)u;
+                bmax[a] = (uint64_t)std::max(FP.n_values[a] - 1, 0);  // (the plain body: no value reaches len(Values))
+            }
+            cshift = lean_moments_fit(na, umax, bmax, slot_rows);  // (one replica always fits: the table is smaller than today's)
+        }
+        if (cshift) {
+            FP.lean |= (int32_t)kLeanMoments;
+            FP.lds_sum_fields = words_lean;
+            FP.cshift = cshift;
+            P.rep_shift = rs;
+            FP.rep_shift = rs;
+            q->lds_bytes = ((size_t)words_lean * (size_t)P.lds_cells * 8) << rs;
+        }
+        if (env("SYBL_PLAN_TRACE")) {
+            fprintf(stderr, "lean moments: lean=%d proved=%d digits=%d mul24=%d cshift=%d count_bits=%d", cshift ? 1 : 0, (FP.lean & (int32_t)kLeanProved) ? 1 : 0,
+                    (int)digits, (int)mul24, cshift, lean_bits(slot_rows));
+            for (int a = 0; a < na && shape; a++)
+                fprintf(stderr, " s%d_bits=%d b%d_bits=%d q%d_bits=%d", a, lean_bits((unsigned __int128)umax[a] * slot_rows), a,
+                        lean_bits((unsigned __int128)bmax[a] * slot_rows), a, lean_bits((unsigned __int128)bmax[a] * bmax[a] * slot_rows));
+            fprintf(stderr, " slot_rows=%lld tried_replicas=%d words=%d replicas=%d\n", (long long)slot_rows, 1 << rs, cshift ? words_lean : words_now,
+                    1 << P.rep_shift);
+        }
     }
 
     // -limit pushed into the scan (pushdown.hip).  Taken when the caller said the rows beyond the limit need nothing but their
@@ -1683,6 +1774,7 @@ struct Planner {
         prefilter_commit();
         if ((rc = select_part_hist(t, q, slot_col, rows_scanned))) return rc;
         plan_count_packing();
+        plan_lean();
         if ((rc = plan_pushdown())) return rc;
         q->stats.rows_scanned = rows_scanned;
         q->stats.blocks_skipped = skipped;

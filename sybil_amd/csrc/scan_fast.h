@@ -62,7 +62,8 @@ struct FastPlan {
     int32_t n_tb, tb_stride;
     int32_t windowed, lds_cells;   // lds_cells == n_cells unless windowed
     int32_t hist_lds;              // kFastHist: bucket arrays as uint32 in LDS (few cells), flushed once
-    int32_t pad_;
+    // k_scan_packed without NUL: what the planner proved about the resident rows (kLean* below; 0 = nothing, SYBL_NO_LEAN=1)
+    int32_t lean;
     // GEN kernels only: validity bitmaps (nullptr = fully populated), int32 group ids (str columns),
     // missing-key cells, and the reject gate / per-aggregation counts of hist_basic.go:104
     const uint32_t *fvalid[kFastMaxF], *gvalid[kFastMaxG], *avalid[kFastMaxA], *tvalid;
@@ -105,7 +106,8 @@ struct FastPlan {
     // k_scan_packed<NUL>: columns with missing rows / str ids / the Info.Min..Max*10 reject gate, rebased:
     // a value is accepted iff alo <= offset <= ahi
     uint32_t alo[kFastMaxA], ahi[kFastMaxA];
-    int32_t nul, pad4_;
+    int32_t nul;
+    int32_t lds_sum_fields;        // kLeanMoments: words per (cell, replica) of the SUM section in LDS (n_sum_fields stays the published count)
     const int32_t *wg_cell_base;
     // The row bitmap of the filter pre-pass (k_prefilter, kernels.hip): bit per physical row, 1 = the row passes the
     // filters the packed bodies do not evaluate themselves (set members, a fifth filter column); nullptr = none.  Read
@@ -120,6 +122,57 @@ struct FastPlan {
 
 hipError_t launch_scan_fast(const FastPlan &P, int nf, int ng, int na, int mode, bool time, bool gen, int n_wg,
                             size_t lds_bytes, hipStream_t st);
+
+// ---- FastPlan::lean: the lean row bodies of k_scan_packed (scan_packed.h), taken on the planner's proofs over the EXACT
+// extrema of the resident rows (planner.cpp: plan_lean).
+//
+// kLeanMoments: moments mode keeps NA + ceil(NA / 2) + NA words per (cell, replica) in LDS instead of 1 + 3 NA, and keeps them
+// next to each other -- [cell][replica][word], where the other layouts are [field][cell][replica] -- so that a row computes one
+// LDS address and every atomic of it is a constant offset away:
+//   S_0           sum of aggregation 0's stored OFFSETS below bit `cshift` (>= 32), Result.Count above it
+//   S_c, c >= 1   sum of aggregation c's offsets
+//   B_j           sum(b) of aggregations 2j (low dword) and 2j + 1 (high dword): the row adds the 64-bit value {b_even, b_odd}
+//   Q_c           sum(b^2) of aggregation c
+// fast_finish unfolds them replica by replica into the published fields (Count, sum(v) = sum(u) + Count * abase, sum(b), sum(b^2)).
+// kLeanProved: every group digit is inside [0, gcard) and every bucket numerator is below 2^24 (and so is the bucket size):
+//   the bodies drop the per-digit compares -- `lcell < ncell` stays -- and the quotient's correction multiplies in 24 bits.
+constexpr uint32_t kLeanMoments = 1u, kLeanProved = 2u;
+constexpr int lean_sum_fields(int na) { return na + (na + 1) / 2 + na; }
+constexpr int lean_bits(unsigned __int128 x) {
+    int b = 0;
+    while (x) b++, x >>= 1;
+    return b;
+}
+// Whether the lean words hold what one (cell, replica) can receive: slot_rows rows, offsets <= umax[c], bucket numbers <= bmax[c].
+// Returns the count's shift (0: does not fit).  S_0 fits as plan_count_packing proves it for avg mode -- sum bits + count bits
+// <= 64, sum bits < 63 -- with the shift raised to 32, where the row's addend is a register pair without any arithmetic.
+constexpr int lean_moments_fit(int na, const uint64_t *umax, const uint64_t *bmax, unsigned __int128 slot_rows) {
+    const unsigned __int128 one = 1;
+    if (na < 1 || slot_rows < 1 || slot_rows >= (one << 63)) return 0;
+    const int sum_bits = lean_bits((unsigned __int128)umax[0] * slot_rows) < 1 ? 1 : lean_bits((unsigned __int128)umax[0] * slot_rows);
+    const int count_bits = lean_bits(slot_rows);
+    if (!(sum_bits + count_bits <= 64 && sum_bits < 63)) return 0;
+    const int shift = sum_bits < 32 ? 32 : sum_bits;
+    if (shift + count_bits > 64) return 0;
+    for (int c = 0; c < na; c++) {
+        if (umax[c] >= (one << 32) || bmax[c] >= (one << 24)) return 0;
+        if (c >= 1 && lean_bits((unsigned __int128)umax[c] * slot_rows) > 64) return 0;                 // S_c
+        if (lean_bits((unsigned __int128)bmax[c] * bmax[c] * slot_rows) > 64) return 0;                 // Q_c
+        // B_j: a dword per member -- the low one's sum must not carry into the high one, the high one's not past the word
+        if ((unsigned __int128)bmax[c] * slot_rows >= (one << 32)) return 0;
+    }
+    return shift;
+}
+namespace lean_check {
+constexpr uint64_t kU0[1] = {0}, kBfit[1] = {65535}, kBnot[1] = {65536};
+// bmax * slot_rows = 65535 * 65537 = 2^32 - 1 fits, 65536 * 65536 = 2^32 does not
+static_assert(lean_moments_fit(1, kU0, kBfit, 65537) == 32, "sum(b) up to 2^32 - 1 fits a dword");
+static_assert(lean_moments_fit(1, kU0, kBnot, 65536) == 0, "sum(b) of 2^32 does not");
+// S_0: 43 sum bits + 21 count bits = 64 fit, 44 + 21 = 65 do not
+constexpr uint64_t kU64[1] = {((uint64_t)1 << 23) - 1}, kU65[1] = {(uint64_t)1 << 23}, kB0[1] = {0};
+static_assert(lean_moments_fit(1, kU64, kB0, (unsigned __int128)1 << 20) == 43, "64 bits of sum and count fit");
+static_assert(lean_moments_fit(1, kU65, kB0, (unsigned __int128)1 << 20) == 0, "65 bits do not");
+}  // namespace lean_check
 
 // ---- partitioned histograms (strategy 5) -------------------------------------------------
 // Full-histogram queries over many cells cannot keep [cell][agg][bucket] in LDS, and one
@@ -573,22 +626,24 @@ __device__ __forceinline__ void fast_row(const FastPlan &P, const FastTile<NF> &
 // LDS layout of one workgroup: [sum fields][max fields][uint32 bucket arrays (hist_lds)], every
 // field replicated 1 << rep_shift times per cell.
 struct FastLds {
-    uint32_t tab_cells, words_sum, words_max, max_base, cell_base, hist_words, rep;
+    uint32_t tab_cells, words_sum, words_max, max_base, cell_base, hist_words, rep;  // (words_sum: the PUBLISHED sum words)
     uint32_t *hist32;
 };
 
 // (T: threads of the workgroup -- the strides of the table loops)
 template <int MODE, int T = kWgThreads>
-__device__ __forceinline__ FastLds fast_begin(const FastPlan &P, int64_t *lds, const bool max32 = false) {
+__device__ __forceinline__ FastLds fast_begin(const FastPlan &P, int64_t *lds, const bool max32 = false, const bool lean = false) {
     FastLds L;
     const uint32_t tid = threadIdx.x;
     const uint32_t R = 1u << P.rep_shift;
     L.tab_cells = (uint32_t)P.lds_cells;
     L.words_sum = (uint32_t)P.n_sum_fields * L.tab_cells;
     L.words_max = (uint32_t)P.n_max_fields * L.tab_cells;
-    L.max_base = L.words_sum << P.rep_shift;
+    // (lean, k_scan_packed in moments mode: the SUM section in LDS has its own word count -- see kLeanMoments)
+    const uint32_t lds_sum = lean ? (uint32_t)P.lds_sum_fields * L.tab_cells : L.words_sum;
+    L.max_base = lds_sum << P.rep_shift;
     L.cell_base = P.windowed ? (uint32_t)P.wg_cell_base[blockIdx.x] : 0u;
-    for (uint32_t i = tid; i < L.words_sum * R; i += T) lds[i] = 0;
+    for (uint32_t i = tid; i < lds_sum * R; i += T) lds[i] = 0;
     // (max32, k_scan_packed in avg mode: the MAX words hold uint32 OFFSETS in their low halves -- see fast_finish)
     for (uint32_t i = tid; i < L.words_max * R; i += T) lds[L.max_base + i] = max32 ? 0 : INT64_MIN;
     L.hist32 = (uint32_t *)(lds + L.max_base + (L.words_max << P.rep_shift));
@@ -603,13 +658,37 @@ __device__ __forceinline__ FastLds fast_begin(const FastPlan &P, int64_t *lds, c
 // table -- flushed with atomics (LDS window) or stored to the workgroup's slice for k_fold.
 // max32 (k_scan_packed, avg mode): the MAX words hold the largest stored OFFSET of the field's aggregation in their low half; the
 // maximum is abase[a] + that offset where the cell's Count is not zero, and untouched (INT64_MIN) where it is.  FastPlan::cshift: Count and aggregation 0's sum of offsets share a word per replica.
+// lean_na > 0 (k_scan_packed in moments mode under kLeanMoments; the kernel's aggregation count): the LDS words are the lean ones.
 template <int T = kWgThreads>
-__device__ __forceinline__ void fast_finish(const FastPlan &P, int64_t *lds, const FastLds &L, uint32_t matched, uint32_t overflow, const bool max32 = false) {
+__device__ __forceinline__ void fast_finish(const FastPlan &P, int64_t *lds, const FastLds &L, uint32_t matched, uint32_t overflow, const bool max32 = false,
+                                            const uint32_t lean_na = 0, const bool derive_overflow = false) {
     const uint32_t tid = threadIdx.x;
     const uint32_t R = 1u << P.rep_shift;
     const uint32_t words_sum = L.words_sum, words_max = L.words_max, tab_cells = L.tab_cells;
     const uint32_t cshift = (uint32_t)P.cshift, f_sum0 = (uint32_t)P.f_sum[0];
-    auto sum_of = [&](uint32_t i) -> int64_t {  // word i of the SUM section, replicas folded
+    auto sum_of = [&](uint32_t i) -> int64_t {  // word i of the (published) SUM section, replicas folded
+        if (lean_na) {
+            // (replica by replica: a low part summed over the replicas may pass its boundary)
+            const uint32_t fi = i / L.tab_cells, c = i - fi * L.tab_cells;
+            const uint32_t W = (uint32_t)lean_sum_fields((int)lean_na);
+            auto word = [&](uint32_t field, uint32_t k) { return (uint64_t)lds[((c << P.rep_shift) + k) * W + field]; };
+            uint64_t cnt = 0;
+            for (uint32_t k = 0; k < R; k++) cnt += word(0, k) >> cshift;
+            if (fi == 0) return (int64_t)cnt;
+            uint64_t acc = 0;
+            for (uint32_t a = 0; a < lean_na; a++) {
+                if (fi == (uint32_t)P.f_sum[a]) {
+                    const uint64_t mask = a == 0 ? ((uint64_t)1 << cshift) - 1 : ~(uint64_t)0;
+                    for (uint32_t k = 0; k < R; k++) acc += word(a, k) & mask;
+                    acc += cnt * (uint64_t)P.abase[a];  // sum(v) = sum(u) + Count * base
+                } else if (fi == (uint32_t)P.f_sb[a]) {
+                    for (uint32_t k = 0; k < R; k++) acc += (a & 1u) ? word(lean_na + a / 2, k) >> 32 : word(lean_na + a / 2, k) & 0xFFFFFFFFull;
+                } else if (fi == (uint32_t)P.f_sb2[a]) {
+                    for (uint32_t k = 0; k < R; k++) acc += word(lean_na + (lean_na + 1) / 2 + a, k);
+                }
+            }
+            return (int64_t)acc;
+        }
         if (cshift) {
             const uint32_t fi = i / L.tab_cells, c = i - fi * L.tab_cells;
             if (fi == 0 || fi == f_sum0) {
@@ -653,11 +732,23 @@ __device__ __forceinline__ void fast_finish(const FastPlan &P, int64_t *lds, con
         matched += __shfl_xor(matched, o, 64);
         overflow += __shfl_xor(overflow, o, 64);
     }
-    {
+    // derive_overflow (k_scan_packed without NUL: every matched row either added one to its cell's Count or was out of bounds, and
+    // no row body counted the latter): the workgroup's overflow is its matched rows minus the Counts of its table -- `counted`
+    // collects the Counts this thread publishes below, and the waves' differences (of either sign) add up in 64 bits.
+    // WARNING: with this, overflow is no independent check of Count.  A row body of a kernel that derives it MUST add exactly
+    // one to published field 0 (its own word, the cshift word or the lean S_0 word) for every live in-bounds row and nothing
+    // otherwise; a body that miscounts, or a count field that wraps, shows up as "rows outside the declared bounds".
+    int64_t counted = 0;
+    auto publish_header = [&]() {
+        if (derive_overflow) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) counted += __shfl_xor(counted, o, 64);
+        }
         const int slot[2] = {kHdrMatched, kHdrOverflow};
-        const int64_t v[2] = {(int64_t)matched, (int64_t)overflow};
+        const int64_t v[2] = {(int64_t)matched, derive_overflow ? (int64_t)overflow + (int64_t)matched - counted : (int64_t)overflow};
         wg_header_add<2>(P.sum_out, slot, v);  // (one atomic per workgroup and counter, not per wave: scan_generic.h)
-    }
+    };
+    if (!derive_overflow) publish_header();
 
     __syncthreads();
     // LDS bucket arrays: one atomic per touched bucket per workgroup into the zeroed global table
@@ -671,6 +762,7 @@ __device__ __forceinline__ void fast_finish(const FastPlan &P, int64_t *lds, con
         int64_t *gs = P.sum_out + kHeaderWords;
         for (uint32_t i = tid; i < words_sum; i += T) {
             const int64_t acc = sum_of(i);
+            if (i < tab_cells) counted += acc;  // (field 0: the cells' Counts)
             if (acc != 0) {
                 const uint32_t fi = i / tab_cells, c = i - fi * tab_cells;
                 __hip_atomic_fetch_add(gs + (int64_t)fi * P.n_cells + L.cell_base + c, acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -683,13 +775,19 @@ __device__ __forceinline__ void fast_finish(const FastPlan &P, int64_t *lds, con
                 __hip_atomic_fetch_max(P.max_out + (int64_t)fi * P.n_cells + L.cell_base + c, acc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
+        if (derive_overflow) publish_header();
         return;
     }
     // fold the lane replicas and publish this workgroup's table (plain stores)
     int64_t *ws = P.ws_sum + (int64_t)blockIdx.x * words_sum;
-    for (uint32_t i = tid; i < words_sum; i += T) ws[i] = sum_of(i);
+    for (uint32_t i = tid; i < words_sum; i += T) {
+        const int64_t acc = sum_of(i);
+        if (i < tab_cells) counted += acc;  // (field 0: the cells' Counts)
+        ws[i] = acc;
+    }
     int64_t *wm = P.ws_max + (int64_t)blockIdx.x * words_max;
     for (uint32_t i = tid; i < words_max; i += T) wm[i] = max_of(i);
+    if (derive_overflow) publish_header();
 }
 
 template <int NF, int NG, int NA, int MODE, bool TIME, bool GEN>

@@ -235,19 +235,30 @@ __device__ __forceinline__ void packed_decode_all(const FastPlan &P0, const Pack
 
 // floor(n / d) for 32-bit n, d >= 1.  inv_lo is 1/d scaled down by (1 - 2^-40), so the product never
 // exceeds the true quotient and is at most 1 short of it: one one-sided correction step is exact.
+// M24 (kLeanProved): n and d are below 2^24, so q <= n is too and q * d <= n cannot wrap -- the correction's product is a
+// 24-bit multiply (full rate) instead of a 32-bit one.
+template <bool M24 = false>
 __device__ __forceinline__ uint32_t packed_udiv(uint32_t n, uint32_t d, double inv_lo) {
     uint32_t q = (uint32_t)((double)n * inv_lo);
-    if (n - q * d >= d) q += 1;
+    if (n - (M24 ? __umul24(q, d) : q * d) >= d) q += 1;
     return q;
 }
 
 // (OUT: the plain body with the outlier test -- a value beyond the last bucket is clipped and remembered, hist_basic.go:132-135:
 // what a fully populated tile of a NUL kernel runs when outliers are the only thing its plan asks of the NUL body)
 // (MAX32: avg mode's maxima as 32-bit OFFSETS -- see the kFastAvgMax branch; the caller has checked !ext_general once per tile)
-template <int NF, int NG, int NA, int MODE, bool TIME, bool NUL, bool FRESH = false, bool OUT = false, bool MAX32 = false>
+// (LEAN, PROVED: FastPlan::lean's kLeanMoments / kLeanProved -- properties of the kernel, see k_scan_packed)
+// matched / overflow: per lane.  (COUNTED: the caller has counted the tile's matched rows itself.  DERIVED: a kernel without NUL,
+// where a matched row either adds one to its cell's Count or is out of bounds -- fast_finish derives the workgroup's overflow
+// from the two, and the row counts nothing.)
+template <int NF, int NG, int NA, int MODE, bool TIME, bool NUL, bool FRESH = false, bool OUT = false, bool MAX32 = false, bool LEAN = false,
+          bool PROVED = false, bool COUNTED = false, bool DERIVED = false>
 __device__ __forceinline__ void packed_row(const FastPlan &P0, const PackedTile<NF> &f, const PackedTile<NG> &g,
                                            const PackedTile<NA> &a, const PackedTile<1> &t, const int r, bool pass, int64_t *lds,
                                            const FastLds &L, uint32_t &matched, uint32_t &overflow, const uint32_t xpop = 0xFu) {
+    static_assert(!LEAN || (MODE == kFastMoments && !NUL && !OUT && NA >= 1), "the lean layout is the plain moments body's");
+    static_assert(!PROVED || (!NUL && !OUT), "proofs cover fully populated rows");
+    static_assert(!DERIVED || (!NUL && !OUT), "only a row that counts in exactly one place can have its overflow derived");
     if (NUL) pass = pass & ((xpop >> r) & 1u);  // the filter pre-pass's verdict (FastPlan::xvalid; all ones without one)
     // no short-circuit anywhere: one predicate, one exec-masked region per row
 #pragma unroll
@@ -279,7 +290,9 @@ __device__ __forceinline__ void packed_row(const FastPlan &P0, const PackedTile<
             inb = inb & (p ? d < (uint32_t)P.gvalues[c] : P.gmissing[c] >= 0);
             cell += p ? __umul24(d, (uint32_t)P.gstride[c]) : (uint32_t)P.gmissing[c];
         } else {
-            inb = inb & (d < P.gcard[c]);
+            // (PROVED: the column's exact extrema lie inside the declared range and the table is not windowed -- `lcell < ncell`
+            // below still keeps a wrong proof from ever writing outside the table)
+            if (!PROVED) inb = inb & (d < P.gcard[c]);
             cell += __umul24(d, (uint32_t)P.gstride[c]);  // aggregate.go:125-143 as a direct-mapped index
         }
     }
@@ -301,12 +314,35 @@ __device__ __forceinline__ void packed_row(const FastPlan &P0, const PackedTile<
     const uint32_t ncell = L.tab_cells;
     const uint32_t lcell = cell - L.cell_base;  // position inside this workgroup's LDS table
     inb = inb & (lcell < ncell);
-    matched += pass ? 1u : 0u;                  // aggregate.go:117
-    overflow += (live & !inb) ? 1u : 0u;
+    if (!COUNTED) matched += pass ? 1u : 0u;  // aggregate.go:117
+    if (!DERIVED) overflow += (live & !inb) ? 1u : 0u;
     if (!(live & inb)) return;
+    const uint32_t rs = (uint32_t)P.rep_shift;
+    if (LEAN) {
+        // kLeanMoments (scan_fast.h): NA + ceil(NA / 2) + NA words, every addend a register or a register pair as it stands --
+        // S_0 takes {u, 1 << (cshift - 32)}, B_j takes {b_even, b_odd}
+        // The words of a (cell, replica) are NEIGHBOURS here (scan_fast.h): one address per row, every atomic a constant offset.
+        constexpr uint32_t kB = NA, kQ = NA + (NA + 1) / 2, kW = (uint32_t)lean_sum_fields(NA);
+        const uint32_t chi = 1u << ((uint32_t)P.cshift - 32u);
+        char *const lean_p = (char *)lds + __umul24((lcell << rs) + L.rep, kW * 8u);
+        auto add = [&](uint32_t field, int64_t v) {
+            __hip_atomic_fetch_add((int64_t *)(lean_p + field * 8u), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        };
+        uint32_t b[NA > 0 ? NA : 1];
+#pragma unroll
+        for (int c = 0; c < NA; c++) {
+            const uint32_t u = a.u[c][r];
+            add((uint32_t)c, (int64_t)(((uint64_t)(c == 0 ? chi : 0u) << 32) | u));  // sum of OFFSETS (c == 0: and Count++)
+            b[c] = packed_udiv<PROVED>(u + P.adoff[c], P.bucket_size[c], P.pinv_bucket[c]);
+            add(kQ + (uint32_t)c, (int64_t)(uint64_t)(uint32_t)__umul24(b[c], b[c]));
+        }
+#pragma unroll
+        for (int j = 0; j < (NA + 1) / 2; j++)
+            add(kB + (uint32_t)j, (int64_t)(((uint64_t)(2 * j + 1 < NA ? b[2 * j + 1 < NA ? 2 * j + 1 : 0] : 0u) << 32) | b[2 * j]));
+        return;
+    }
     // byte address of the cell's Count word; every other field of the cell is a wave-uniform byte
     // offset away (one VALU add per atomic)
-    const uint32_t rs = (uint32_t)P.rep_shift;
     char *const cell_p = (char *)lds + (((lcell << rs) + L.rep) << 3);
     const uint32_t fstep = (ncell << rs) << 3;  // bytes between consecutive fields
     auto add = [&](uint32_t field, int64_t v) {
@@ -360,7 +396,7 @@ __device__ __forceinline__ void packed_row(const FastPlan &P0, const PackedTile<
         if (MODE == kFastMoments || MODE == kFastHist) {
             // bucket_value := (value - h.Min) / BucketSize, hist_basic.go:130; the planner guarantees
             // 0 <= value - h.Min < 2^32 and that no value reaches len(Values)
-            uint32_t b = packed_udiv(u + P.adoff[c], P.bucket_size[c], P.pinv_bucket[c]);
+            uint32_t b = packed_udiv<PROVED>(u + P.adoff[c], P.bucket_size[c], P.pinv_bucket[c]);
             if ((NUL || OUT) && b >= (uint32_t)P.n_values[c]) {
                 // Outlier (hist_basic.go:132-135; BucketSize = size / 1000 truncates, so the top of many a column's range
                 // lies beyond the last bucket): clipped into the last bucket AND remembered as exact n, sum(o), sum(o^2)
@@ -394,6 +430,25 @@ __device__ __forceinline__ void packed_row(const FastPlan &P0, const PackedTile<
     }
 }
 
+// The four rows of a tile of a kernel without NUL (overflow is derived, see packed_row) through its plain body.  pass(k): row
+// k's predicate so far.  max32: kFastAvgMax && !ext_general (wave-uniform, once per tile); LEANV: the kernel's (k_scan_packed).
+// COUNTED: the caller counts the tile's matched rows per lane (where that is one instruction per tile).
+template <int NF, int NG, int NA, int MODE, bool TIME, bool FRESH, bool COUNTED, int LEANV, class PASS>
+__device__ __forceinline__ void packed_plain_tile(const FastPlan &P, const PackedTile<NF> &f, const PackedTile<NG> &g, const PackedTile<NA> &a,
+                                                  const PackedTile<1> &t, PASS pass, int64_t *lds, const FastLds &L, const bool max32,
+                                                  uint32_t &matched, uint32_t &overflow) {
+    constexpr bool kLean = (LEANV & kLeanMoments) != 0, kProved = (LEANV & kLeanProved) != 0;
+    if (MODE == kFastAvgMax && max32) {
+#pragma unroll
+        for (int k = 0; k < kPackedRows; k++)
+            packed_row<NF, NG, NA, MODE, TIME, false, FRESH, false, true, false, false, COUNTED, true>(P, f, g, a, t, k, pass(k), lds, L, matched, overflow);
+    } else {
+#pragma unroll
+        for (int k = 0; k < kPackedRows; k++)
+            packed_row<NF, NG, NA, MODE, TIME, false, FRESH, false, false, kLean, kProved, COUNTED, true>(P, f, g, a, t, k, pass(k), lds, L, matched, overflow);
+    }
+}
+
 constexpr int64_t kPackedChunkRows = (int64_t)1 << 28;  // rows addressed with one 32-bit byte offset (x4 bytes)
 
 // SYBL_PACKED_LATE=0 at build time: k_scan_packed without late materialisation (same-box A/B builds)
@@ -413,13 +468,20 @@ constexpr bool kPackedLateBranch = SYBL_PACKED_LATE_BRANCH != 0;
 #ifndef SYBL_PACKED_WAVES_PER_EU
 #define SYBL_PACKED_WAVES_PER_EU 4
 #endif
-template <int NF, int NG, int NA, int MODE, bool TIME, bool G1, bool NUL, int RING = 0>
+// LEANV: what the planner proved for this launch (FastPlan::lean: kLeanMoments | kLeanProved) as a property of the KERNEL -- the
+// launcher picks the instantiation, and a lean kernel holds the lean body only.  (Two bodies chosen per tile inside one loop
+// cost the loop 20 more spilled scalar registers; DESIGN 3.6 has the same finding for two loops in one kernel.)
+template <int NF, int NG, int NA, int MODE, bool TIME, bool G1, bool NUL, int RING = 0, int LEANV = 0>
 __global__ __launch_bounds__(kWgThreads, SYBL_PACKED_WAVES_PER_EU) void k_scan_packed(const FastPlan P) {
+    static_assert(LEANV == 0 || !NUL, "the NUL kernels mix row bodies: no proofs");
+    static_assert(!(LEANV & kLeanMoments) || (MODE == kFastMoments && NA >= 1), "the lean layout is moments mode's");
+    static_assert(!(LEANV & kLeanProved) || MODE == kFastMoments || MODE == kFastHist, "the proved bodies are the bucket modes'");
     extern __shared__ int64_t lds[];
     const uint32_t tid = threadIdx.x;
     // avg mode, every value populated (the NUL kernels mix row bodies: they keep 64-bit maxima): maxima as 32-bit offsets
     constexpr bool kMax32 = MODE == kFastAvgMax && !NUL;
-    const FastLds L = fast_begin<MODE>(P, lds, kMax32 && !P.ext_general);
+    constexpr bool lean_layout = (LEANV & kLeanMoments) != 0;
+    const FastLds L = fast_begin<MODE>(P, lds, kMax32 && !P.ext_general, lean_layout);
 
     uint32_t matched = 0, overflow = 0;
     const int s0 = P.wg_seg_begin[blockIdx.x], s1 = P.wg_seg_begin[blockIdx.x + 1];
@@ -465,15 +527,8 @@ __global__ __launch_bounds__(kWgThreads, SYBL_PACKED_WAVES_PER_EU) void k_scan_p
                         packed_decode_all<NF, NG, NA, TIME, G1, false>(P, rf[d], rg[d], ra[d], rt[d], f, g, a, t, 0u);
                         packed_issue_ring<NF, NG, NA, TIME, G1>(P, B, r + (uint32_t)D * kPackedTileRows, n, rf[d], rg[d], ra[d], rt[d]);
                         const uint32_t left = r < n ? n - r : 0u;
-                        if (kMax32 && !P.ext_general) {  // (wave-uniform, once per tile)
-#pragma unroll
-                            for (int k = 0; k < kPackedRows; k++)
-                                packed_row<NF, NG, NA, MODE, TIME, false, false, false, true>(P, f, g, a, t, k, (uint32_t)k < left, lds, L, matched, overflow);
-                        } else {
-#pragma unroll
-                            for (int k = 0; k < kPackedRows; k++)
-                                packed_row<NF, NG, NA, MODE, TIME, false>(P, f, g, a, t, k, (uint32_t)k < left, lds, L, matched, overflow);
-                        }
+                        packed_plain_tile<NF, NG, NA, MODE, TIME, false, false, LEANV>(P, f, g, a, t, [&](int k) { return (uint32_t)k < left; }, lds, L,
+                                                                                kMax32 && !P.ext_general, matched, overflow);
                     }
                 }
                 continue;
@@ -585,15 +640,9 @@ __global__ __launch_bounds__(kWgThreads, SYBL_PACKED_WAVES_PER_EU) void k_scan_p
                         issue_rest(r + kPackedTileRows, __builtin_amdgcn_ballot_w64(next_bits != 0) != 0);
                     }
                     issue_filters(r + 2u * kPackedTileRows);
-                    if (kMax32 && !P.ext_general) {  // (wave-uniform, once per tile)
-#pragma unroll
-                        for (int k = 0; k < kPackedRows; k++)
-                            packed_row<0, NG, NA, MODE, TIME, false, false, false, true>(P, f0, g, a, t, k, (bits >> k) & 1u, lds, L, matched, overflow);
-                    } else {
-#pragma unroll
-                        for (int k = 0; k < kPackedRows; k++)
-                            packed_row<0, NG, NA, MODE, TIME, false>(P, f0, g, a, t, k, (bits >> k) & 1u, lds, L, matched, overflow);
-                    }
+                    matched += (uint32_t)__builtin_popcount(bits);  // aggregate.go:117, the lane's rows of this tile at once
+                    packed_plain_tile<0, NG, NA, MODE, TIME, false, true, LEANV>(P, f0, g, a, t, [&](int k) -> bool { return (bits >> k) & 1u; }, lds, L,
+                                                                                 kMax32 && !P.ext_general, matched, overflow);
                     bits = next_bits;
                 }
                 continue;
@@ -636,10 +685,10 @@ __global__ __launch_bounds__(kWgThreads, SYBL_PACKED_WAVES_PER_EU) void k_scan_p
 #pragma unroll
                     for (int k = 0; k < kPackedRows; k++)
                         packed_row<NF, NG, NA, MODE, TIME, false, FRESH, true>(P, f, g, a, t, k, (uint32_t)k < left, lds, L, matched, overflow);
-                } else if (kMax32 && !P.ext_general) {  // (wave-uniform, once per tile; kMax32: not a NUL kernel)
-#pragma unroll
-                    for (int k = 0; k < kPackedRows; k++)
-                        packed_row<NF, NG, NA, MODE, TIME, false, FRESH, false, true>(P, f, g, a, t, k, (uint32_t)k < left, lds, L, matched, overflow);
+                } else if constexpr (!NUL) {  // (the plain body the plan allows: wave-uniform, once per tile)
+                    if (NF == 0) matched += left < (uint32_t)kPackedRows ? left : (uint32_t)kPackedRows;  // no filter: every row of the tile
+                    packed_plain_tile<NF, NG, NA, MODE, TIME, FRESH, NF == 0, LEANV>(P, f, g, a, t, [&](int k) { return (uint32_t)k < left; }, lds, L,
+                                                                              kMax32 && !P.ext_general, matched, overflow);
                 } else {
 #pragma unroll
                     for (int k = 0; k < kPackedRows; k++)
@@ -650,7 +699,8 @@ __global__ __launch_bounds__(kWgThreads, SYBL_PACKED_WAVES_PER_EU) void k_scan_p
             }
         }
     }
-    fast_finish(P, lds, L, matched, overflow, kMax32 && !P.ext_general);
+    // (!NUL: no row body counted overflow -- fast_finish derives it)
+    fast_finish(P, lds, L, matched, overflow, kMax32 && !P.ext_general, lean_layout ? (uint32_t)NA : 0u, !NUL);
 }
 
 // k_emit over compact storage (strategy 5, see k_emit in scan_fast.h): the same records, staged and
@@ -1083,6 +1133,29 @@ static hipError_t packed_launch_k1(const FastPlan &P, int n_wg, size_t lds_bytes
     constexpr bool kAb = !NUL && ((NF == 3 && NG == 2 && NA == 2 && MODE == kFastMoments && !TIME && G1) ||
                                   (NF == 0 && NG == 1 && NA == 2 && MODE == kFastAvgMax && !TIME && G1) ||
                                   (NF == 0 && NG == 1 && NA == 1 && MODE == kFastAvg && TIME && !G1));
+    auto launch_lean = [&](auto kern) {
+        hipError_t e2 = hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        if (e2 != hipSuccess) return e2;
+        hipLaunchKernelGGL(kern, dim3(n_wg), dim3(kWgThreads), lds_bytes, st, P);
+        return hipGetLastError();
+    };
+    // FastPlan::lean: the kernel must be the one the planner sized the table for.  (The lean kernels have no ring variants:
+    // SYBL_PACKED_RING acts on a plan without lean -- set SYBL_NO_LEAN=1 beside it.)
+    if (P.lean) {
+        if constexpr (!NUL && NA >= 1 && MODE == kFastMoments) {
+            switch (P.lean) {
+            case kLeanMoments: return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, NUL, 0, kLeanMoments>);
+            case kLeanProved: return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, NUL, 0, kLeanProved>);
+            case kLeanMoments | kLeanProved: return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, NUL, 0, kLeanMoments | kLeanProved>);
+            default: return hipErrorInvalidValue;
+            }
+        } else if constexpr (!NUL && NA >= 1 && MODE == kFastHist) {
+            if (P.lean != kLeanProved) return hipErrorInvalidValue;
+            return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, NUL, 0, kLeanProved>);
+        } else {
+            return hipErrorInvalidValue;  // (the planner sets it for those kernels only)
+        }
+    }
     if (kAb) {
         if (const char *e = env("SYBL_PACKED_RING")) {
             const int d = atoi(e);
