@@ -644,6 +644,56 @@ typedef struct {
 } sybl_digest_stats;
 int sybl_table_digest_stats(const sybl_table *t, sybl_digest_stats *out);
 
+/* ------------------------------------------------------------------ select
+ * The rows of a resident table that pass a filter, as a NEW resident table: what keeps a subset of a table in HBM.  Its uses:
+ * retention for resident tables (select time > T, free the old table -- the reference trims whole blocks, table_trim.go);
+ * materialising an expensive filter once, so that the queries behind it are plain scans of a smaller table; and, followed by
+ * sybl_table_save, the export of a subset in the reference's format (-export, table_query.go:204).  The filter pass, the row
+ * list and the gather of every column run on the GPU (csrc/select.hip).  Restated deterministically:
+ *   source rows: the logical rows of the live blocks in resident order, r = 0..N-1.  Blocks without rows (left behind by
+ *     sybl_table_refresh) and the padding of a block to 32 rows contribute nothing.
+ *   matching: a row matches when it passes every filter, evaluated exactly as the aggregate path and samples do: ANDed,
+ *     strict, an unpopulated value fails.  Without filters every row matches (the call then re-cuts the table into other
+ *     block sizes).  When the planner proves that no row can match (x > INT64_MAX, an operator the column's type does not
+ *     have) the output has the columns and no blocks, and no kernel runs; filters it does not see through (x > 5 AND x < 3)
+ *     run the kernels, find M = 0 and give the same output.  Filters on more than 8 distinct columns: SYBL_E_INVAL (as
+ *     for samples).
+ *   output rows: the matching rows in ascending source order, s_0 < s_1 < .. < s_(M-1).  Output block j holds
+ *     s_[j * block_rows, min(M, (j+1) * block_rows)).  M = 0: the columns and no blocks.
+ *   block_rows: 0 = 65536; 1..65536 as given; anything else: SYBL_E_INVAL.
+ *   columns: the output holds the named columns in the order named, each once (a name given again is ignored); NULL or 0 =
+ *     every column in table order; a name the table does not hold: SYBL_E_INVAL.  A filter column need not be an output column.
+ * Every output column inherits, by digest's rules: type, IntInfo, declared bounds (sybl_table_set_bounds) and has_missing;
+ * the str / set dictionary copied id for id; compact storage iff the source is in compact mode, with the source column's
+ * (width, base) kept (every output value is a source value); a validity bitmap iff the source column has one.  Per-block
+ * min / max / populated counts are exact for the new blocks; table-wide extrema may be the source's.
+ * The output has the source's ctx and name, is attached to no directory, owns everything it shows and outlives the source;
+ * free it with sybl_table_free.  The source is untouched and its version does not move: prepared queries on it stay valid.
+ * Rank-local, never collective; runs on the ctx stream and is complete on return.  More than 2^32 - 1 physical rows in the
+ * source, dead blocks included: SYBL_E_INVAL (row numbers travel as 32 bits; nothing is sorted, so no 2^31 limit applies).
+ * The call needs a bit per source row, 4 bytes per matching row and the output; when HBM runs out it returns SYBL_E_NOMEM,
+ * frees everything it allocated and leaves *out NULL.  NULL arguments are errors. */
+typedef struct {
+    int32_t n_filters;
+    const sybl_filter *filters;   /* as in sybl_query_desc / sybl_samples_desc */
+    int32_t n_columns;
+    const char *const *columns;   /* columns of the output; NULL / 0 = every column */
+    int32_t block_rows;           /* 0 = 65536; 1..65536 as given */
+} sybl_select_desc;
+
+int sybl_table_select(sybl_table *t, const sybl_select_desc *d, sybl_table **out);
+
+/* Where the device time of the sybl_table_select that made this table went (zeros for any other table), and the bytes each
+ * phase moves, computed from the shapes. */
+typedef struct {
+    int64_t rows_in, rows_out, blocks_in, blocks_out;  /* N, M, live source blocks, output blocks */
+    double filter_ms;      /* hipEvent time: bitmap memset + k_prefilter (0 without filters) */
+    double rows_ms;        /* ... k_sel_count + k_sel_rows (the readback between them is not in it) */
+    double gather_ms;      /* ... gather of every output column, validity words and block statistics */
+    int64_t filter_bytes, rows_bytes, gather_bytes;
+} sybl_select_stats;
+int sybl_table_select_stats(const sybl_table *t, sybl_select_stats *out);
+
 /* Test hook (no GPU needed): the library's regular-expression engine for re / nre str filters -- Go regexp
  * (RE2) syntax, unanchored search like regexp.MatchString (filter.go:213-236).  1 = match, 0 = no match,
  * -1 = the pattern does not compile (sybl_last_error says why). */

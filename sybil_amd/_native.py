@@ -127,6 +127,20 @@ class DigestStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class SelectDesc(C.Structure):
+    _fields_ = [("n_filters", C.c_int32), ("filters", C.POINTER(Filter)), ("n_columns", C.c_int32),
+                ("columns", C.POINTER(C.c_char_p)), ("block_rows", C.c_int32)]
+
+
+class SelectStats(C.Structure):
+    _fields_ = [("rows_in", C.c_int64), ("rows_out", C.c_int64), ("blocks_in", C.c_int64), ("blocks_out", C.c_int64),
+                ("filter_ms", C.c_double), ("rows_ms", C.c_double), ("gather_ms", C.c_double), ("filter_bytes", C.c_int64),
+                ("rows_bytes", C.c_int64), ("gather_bytes", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol include/sybilgpu.h declares: (restype, argtypes)
 P = C.c_void_p
 SIGNATURES = {
@@ -207,6 +221,8 @@ SIGNATURES = {
     "sybl_samples_render": (C.c_char_p, [P]),
     "sybl_table_digest": (C.c_int, [P, C.c_char_p, C.c_int32, C.POINTER(P)]),
     "sybl_table_digest_stats": (C.c_int, [P, C.POINTER(DigestStats)]),
+    "sybl_table_select": (C.c_int, [P, C.POINTER(SelectDesc), C.POINTER(P)]),
+    "sybl_table_select_stats": (C.c_int, [P, C.POINTER(SelectStats)]),
 }
 
 _lib = None

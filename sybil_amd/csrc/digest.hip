@@ -19,6 +19,9 @@
 //
 // Set columns: validity as above; the CSR (Column::h_set_off / h_set_vals, the host mirror every upload starts from) is
 // gathered on the host from the permutation.
+//
+// Everything behind the sort -- layout, gather, validity, statistics, set columns, the block writer -- is gather_rows
+// (gather.h): select.hip runs it over its ascending row list and a column subset.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
@@ -26,6 +29,7 @@
 #include <new>
 
 #include "engine.h"
+#include "gather.h"
 
 namespace sybl {
 
@@ -117,41 +121,6 @@ __global__ __launch_bounds__(kDgThreads) void k_dg_valid(const uint32_t *__restr
 
 namespace {
 
-// everything a run allocates on the device, freed on every exit
-struct DevPool {
-    std::vector<void *> ptrs;
-    std::vector<hipEvent_t> events;
-    ~DevPool() {
-        for (void *p : ptrs) (void)hipFree(p);
-        for (hipEvent_t e : events) (void)hipEventDestroy(e);
-    }
-    template <typename T>
-    int alloc(T **out, size_t n, const char *what) {
-        void *p = nullptr;
-        hipError_t e = hipMalloc(&p, std::max<size_t>(n, 1) * sizeof(T));
-        if (e != hipSuccess) return hip_fail(e, what);  // (out of memory: SYBL_E_NOMEM)
-        ptrs.push_back(p);
-        *out = (T *)p;
-        return SYBL_OK;
-    }
-    int event(hipEvent_t *out, hipStream_t st) {
-        hipEvent_t e = nullptr;
-        SYBL_HIP(hipEventCreate(&e));
-        events.push_back(e);
-        SYBL_HIP(hipEventRecord(e, st));
-        *out = e;
-        return SYBL_OK;
-    }
-};
-
-// the output table, freed on every exit unless it is handed to the caller
-struct TableOwner {
-    sybl_table *t = nullptr;
-    ~TableOwner() {
-        if (t) sybl_table_free(t);
-    }
-};
-
 inline unsigned grid_for(int64_t n, int threads) { return (unsigned)std::max<int64_t>(1, (n + threads - 1) / threads); }
 inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
@@ -173,17 +142,12 @@ void launch_gather(const void *src, const uint32_t *perm, int64_t N, int64_t blo
                        dst);
 }
 
-int run(Table *t, Column *tc, int64_t block_rows, Table *o, sybl_digest_stats *S) {
-    Ctx *ctx = t->ctx;
-    hipStream_t st = ctx->stream;
-    int rc;
-    if ((rc = load_sync_all(ctx))) return rc;
-    if ((rc = table_ensure_stats(t))) return rc;  // (the key column's extrema; the table's version does not move)
+}  // namespace
 
-    // ---- the output's columns: name, type, IntInfo, dictionaries, declared bounds, storage
+// (gather.h) name, type, IntInfo, dictionaries, declared bounds, storage
+void gather_make_columns(const Table *t, const std::vector<Column *> &src, Table *o) {
     o->compact_mode = t->compact_mode;
-    for (auto &cp : t->cols) {
-        const Column *c = cp.get();
+    for (const Column *c : src) {
         auto n = std::make_unique<Column>();
         n->name = c->name;
         n->type = c->type;
@@ -201,6 +165,160 @@ int run(Table *t, Column *tc, int64_t block_rows, Table *o, sybl_digest_stats *S
         o->col_ix[n->name] = (int)o->cols.size();
         o->cols.push_back(std::move(n));
     }
+}
+
+// (gather.h) the back half of a digest, shared with select.hip: there the row list is ascending, here it is the sort's
+// permutation -- the name it keeps below
+int gather_rows(Table *t, const std::vector<Column *> &src, const uint32_t *perm, int64_t N, int64_t block_rows, Table *o, GatherPool &pool,
+                const char *who, hipEvent_t *gathered, int64_t *bytes, int64_t *blocks) {
+    Ctx *ctx = t->ctx;
+    hipStream_t st = ctx->stream;
+    int rc;
+
+    // ---- the output's layout: block j at physical row j * stride, as the block writer will place it
+    const int64_t stride = round_up(block_rows, 32);
+    const int64_t nb_out = (N + block_rows - 1) / block_rows;
+    const int64_t last_n = N - (nb_out - 1) * block_rows;
+    const int64_t phys_out = (nb_out - 1) * stride + last_n;
+    const int64_t n_out = round_up(phys_out, 32), n_words = n_out / 32;
+    std::vector<Segment> osegs((size_t)nb_out);
+    for (int64_t j = 0; j < nb_out; j++) osegs[(size_t)j] = Segment{j * stride, j + 1 < nb_out ? block_rows : last_n};
+
+    // ---- gather: every column whole, into its final place; validity words into scratch (the writer sets a block's words
+    // when the block is begun: the gathered words are copied over them at the end)
+    const size_t nc = src.size();
+    std::vector<uint32_t *> vbits(nc, nullptr);
+    const bool want_stats = o->compact_mode;  // (canonical storage: table_ensure_stats computes them on first use, as for appended blocks)
+    Segment *d_osegs = nullptr;
+    int64_t *d_stats = nullptr;
+    if (want_stats) {
+        if ((rc = pool.alloc(&d_osegs, (size_t)nb_out, "gather blocks"))) return rc;
+        if ((rc = pool.alloc(&d_stats, nc * 3 * (size_t)nb_out, "gather statistics"))) return rc;
+        if ((rc = host_to_device(ctx, d_osegs, osegs.data(), osegs.size() * sizeof(Segment), "gather blocks"))) return rc;
+    }
+    for (size_t k = 0; k < nc; k++) {
+        const Column *c = src[k];
+        Column *n = o->cols[k].get();
+        if (c->d_valid) {
+            if ((rc = pool.alloc(&vbits[k], (size_t)n_words, "gather validity"))) return rc;
+            if ((rc = valid_reserve(o, n, phys_out))) return rc;
+            hipLaunchKernelGGL(k_dg_valid, dim3(grid_for(n_out, kDgThreads)), dim3(kDgThreads), 0, st, (const uint32_t *)c->d_valid,
+                               (const uint32_t *)perm, N, block_rows, stride, n_words, vbits[k]);
+            *bytes += N * 4 + N * 4 + n_words * 4;  // (a 32-byte sector per source bit is what the memory sees: counted as a word)
+        }
+        if (c->type == SYBL_SET_VAL) continue;
+        if ((rc = table_reserve(o, n, phys_out))) return rc;
+        if (!c->d_data) {
+            SYBL_HIP(hipMemsetAsync(n->d_data, 0, (size_t)n_out * (size_t)n->elem, st));
+        } else {
+            switch (c->elem) {
+            case 8: launch_gather<8>(c->d_data, perm, N, block_rows, stride, n_out, n->d_data, st); break;
+            case 4: launch_gather<4>(c->d_data, perm, N, block_rows, stride, n_out, n->d_data, st); break;
+            case 2: launch_gather<2>(c->d_data, perm, N, block_rows, stride, n_out, n->d_data, st); break;
+            default: launch_gather<1>(c->d_data, perm, N, block_rows, stride, n_out, n->d_data, st); break;
+            }
+            *bytes += N * 4 + 2 * N * (int64_t)c->elem;
+        }
+        SYBL_HIP(hipGetLastError());
+        if (want_stats) {
+            int64_t *out = d_stats + k * 3 * (size_t)nb_out;
+            hipError_t e = launch_block_minmax(n->d_data, n->elem, n->vbase, vbits[k], d_osegs, (int)nb_out, out, out + nb_out, out + 2 * nb_out, st);
+            if (e != hipSuccess) return hip_fail(e, "k_block_minmax");
+        }
+    }
+    if ((rc = pool.event(gathered, st))) return rc;
+    std::vector<int64_t> stats;
+    if (want_stats) {
+        stats.resize(nc * 3 * (size_t)nb_out);
+        SYBL_HIP(hipMemcpyAsync(stats.data(), d_stats, stats.size() * 8, hipMemcpyDeviceToHost, st));
+    }
+    SYBL_HIP(hipStreamSynchronize(st));  // the ONE wait for the statistics of every block of every column
+
+    // ---- set columns: the host CSR over the output's physical rows, gathered from the permutation
+    bool any_set = false;
+    for (const Column *c : src) any_set = any_set || c->type == SYBL_SET_VAL;
+    if (any_set) {
+        std::vector<uint32_t> hperm((size_t)N);
+        SYBL_HIP(hipMemcpy(hperm.data(), perm, (size_t)N * 4, hipMemcpyDeviceToHost));
+        for (size_t k = 0; k < nc; k++) {
+            const Column *c = src[k];
+            Column *n = o->cols[k].get();
+            if (c->type != SYBL_SET_VAL) continue;
+            n->h_set_off.assign(1, 0);
+            n->h_set_off.reserve((size_t)phys_out + 1);
+            for (int64_t j = 0; j < nb_out; j++) {
+                const int64_t rows = j + 1 < nb_out ? stride : last_n;  // (padding rows: empty sets; the table ends with its last row)
+                for (int64_t r = 0; r < rows; r++) {
+                    const int64_t i = j * block_rows + r;
+                    if (r < block_rows && i < N) {
+                        const size_t s = hperm[(size_t)i];
+                        if (s + 1 < c->h_set_off.size())
+                            n->h_set_vals.insert(n->h_set_vals.end(), c->h_set_vals.begin() + c->h_set_off[s], c->h_set_vals.begin() + c->h_set_off[s + 1]);
+                    }
+                    n->h_set_off.push_back((int64_t)n->h_set_vals.size());
+                }
+            }
+            n->set_dirty = true;
+        }
+    }
+
+    // ---- the block writer: segments, block statistics, versions.  Nothing here waits for the GPU.
+    for (int64_t j = 0; j < nb_out; j++) {
+        const Segment &sg = osegs[(size_t)j];
+        BlockWriter w;
+        if ((rc = block_begin(o, sg.n, &w))) return rc;
+        if (w.start != sg.start) return fail(SYBL_E_STATE, "%s: block %lld begins at row %lld, not %lld", who, (long long)j, (long long)w.start, (long long)sg.start);
+        for (size_t k = 0; k < nc; k++) {
+            Column *n = o->cols[k].get();
+            void *col = nullptr;
+            uint32_t *valid = nullptr;
+            // all_populated: the writer leaves the rows alone (they are in place) and sets the block's validity words, if the
+            // column has any, to ones -- the gathered words replace them below
+            bool direct = false;
+            if (want_stats && n->type != SYBL_SET_VAL) {
+                const int64_t *h = stats.data() + k * 3 * (size_t)nb_out;
+                const int64_t mn = h[j], mx = h[nb_out + j], pop = h[2 * nb_out + j];
+                if ((rc = block_col_direct(w, n, true, mn, mx, pop, &col, &valid, &direct))) return rc;
+                if (!direct) {
+                    // (SYBL_NO_DIRECT_DECODE: through the staging block -- the rows in place, decoded, and packed back at commit)
+                    if ((rc = block_col_device(w, n, true, &col, &valid))) return rc;
+                    hipError_t e = launch_repack((const char *)n->d_data + (size_t)sg.start * (size_t)n->elem, n->elem, n->vbase, col, n->canon(), 0, sg.n, st);
+                    if (e != hipSuccess) return hip_fail(e, "k_repack");
+                    block_col_stats(w, n, mn, mx, pop);
+                    continue;
+                }
+            } else if ((rc = block_col_device(w, n, true, &col, &valid))) {
+                return rc;
+            }
+            if (n->type != SYBL_SET_VAL && col != (char *)n->d_data + (size_t)sg.start * (size_t)n->elem)
+                return fail(SYBL_E_STATE, "%s: column '%s' moved under the writer", who, n->name.c_str());
+        }
+        if ((rc = block_commit(w))) return rc;
+    }
+    for (size_t k = 0; k < nc; k++) {
+        Column *n = o->cols[k].get();
+        if (!vbits[k]) continue;
+        SYBL_HIP(hipMemcpyAsync(n->d_valid, vbits[k], (size_t)n_words * 4, hipMemcpyDeviceToDevice, st));
+        n->has_missing = n->has_missing || src[k]->has_missing;
+    }
+    SYBL_HIP(hipStreamSynchronize(st));
+    *blocks = nb_out;
+    return SYBL_OK;
+}
+
+namespace {
+
+int run(Table *t, Column *tc, int64_t block_rows, Table *o, sybl_digest_stats *S) {
+    Ctx *ctx = t->ctx;
+    hipStream_t st = ctx->stream;
+    int rc;
+    if ((rc = load_sync_all(ctx))) return rc;
+    if ((rc = table_ensure_stats(t))) return rc;  // (the key column's extrema; the table's version does not move)
+
+    // ---- the output's columns: every column of the source, in its order
+    std::vector<Column *> src;
+    for (auto &cp : t->cols) src.push_back(cp.get());
+    gather_make_columns(t, src, o);
 
     // ---- the source rows: the live blocks in resident order
     std::vector<DgBlock> live;
@@ -217,7 +335,7 @@ int run(Table *t, Column *tc, int64_t block_rows, Table *o, sybl_digest_stats *S
     if (N == 0) return SYBL_OK;
     const int nb_src = (int)live.size();
 
-    DevPool pool;
+    GatherPool pool;
     hipEvent_t ev[4];
 
     // ---- keys
@@ -263,139 +381,13 @@ int run(Table *t, Column *tc, int64_t block_rows, Table *o, sybl_digest_stats *S
     else SYBL_HIP(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, (uint32_t *)key0, (uint32_t *)key1, row0, perm, (int)N, 0, bits, st));
     if ((rc = pool.event(&ev[2], st))) return rc;
 
-    // ---- the output's layout: block j at physical row j * stride, as the block writer will place it
-    const int64_t stride = round_up(block_rows, 32);
-    const int64_t nb_out = (N + block_rows - 1) / block_rows;
-    const int64_t last_n = N - (nb_out - 1) * block_rows;
-    const int64_t phys_out = (nb_out - 1) * stride + last_n;
-    const int64_t n_out = round_up(phys_out, 32), n_words = n_out / 32;
-    std::vector<Segment> osegs((size_t)nb_out);
-    for (int64_t j = 0; j < nb_out; j++) osegs[(size_t)j] = Segment{j * stride, j + 1 < nb_out ? block_rows : last_n};
-
-    // ---- gather: every column whole, into its final place; validity words into scratch (the writer sets a block's words
-    // when the block is begun: the gathered words are copied over them at the end)
-    const size_t nc = t->cols.size();
-    std::vector<uint32_t *> vbits(nc, nullptr);
-    const bool want_stats = o->compact_mode;  // (canonical storage: table_ensure_stats computes them on first use, as for appended blocks)
-    Segment *d_osegs = nullptr;
-    int64_t *d_stats = nullptr;
-    if (want_stats) {
-        if ((rc = pool.alloc(&d_osegs, (size_t)nb_out, "digest blocks"))) return rc;
-        if ((rc = pool.alloc(&d_stats, nc * 3 * (size_t)nb_out, "digest statistics"))) return rc;
-        if ((rc = host_to_device(ctx, d_osegs, osegs.data(), osegs.size() * sizeof(Segment), "digest blocks"))) return rc;
-    }
-    for (size_t k = 0; k < nc; k++) {
-        const Column *c = t->cols[k].get();
-        Column *n = o->cols[k].get();
-        if (c->d_valid) {
-            if ((rc = pool.alloc(&vbits[k], (size_t)n_words, "digest validity"))) return rc;
-            if ((rc = valid_reserve(o, n, phys_out))) return rc;
-            hipLaunchKernelGGL(k_dg_valid, dim3(grid_for(n_out, kDgThreads)), dim3(kDgThreads), 0, st, (const uint32_t *)c->d_valid,
-                               (const uint32_t *)perm, N, block_rows, stride, n_words, vbits[k]);
-            S->gather_bytes += N * 4 + N * 4 + n_words * 4;  // (a 32-byte sector per source bit is what the memory sees: counted as a word)
-        }
-        if (c->type == SYBL_SET_VAL) continue;
-        if ((rc = table_reserve(o, n, phys_out))) return rc;
-        if (!c->d_data) {
-            SYBL_HIP(hipMemsetAsync(n->d_data, 0, (size_t)n_out * (size_t)n->elem, st));
-        } else {
-            switch (c->elem) {
-            case 8: launch_gather<8>(c->d_data, perm, N, block_rows, stride, n_out, n->d_data, st); break;
-            case 4: launch_gather<4>(c->d_data, perm, N, block_rows, stride, n_out, n->d_data, st); break;
-            case 2: launch_gather<2>(c->d_data, perm, N, block_rows, stride, n_out, n->d_data, st); break;
-            default: launch_gather<1>(c->d_data, perm, N, block_rows, stride, n_out, n->d_data, st); break;
-            }
-            S->gather_bytes += N * 4 + 2 * N * (int64_t)c->elem;
-        }
-        SYBL_HIP(hipGetLastError());
-        if (want_stats) {
-            int64_t *out = d_stats + k * 3 * (size_t)nb_out;
-            hipError_t e = launch_block_minmax(n->d_data, n->elem, n->vbase, vbits[k], d_osegs, (int)nb_out, out, out + nb_out, out + 2 * nb_out, st);
-            if (e != hipSuccess) return hip_fail(e, "k_block_minmax");
-        }
-    }
-    if ((rc = pool.event(&ev[3], st))) return rc;
-    std::vector<int64_t> stats;
-    if (want_stats) {
-        stats.resize(nc * 3 * (size_t)nb_out);
-        SYBL_HIP(hipMemcpyAsync(stats.data(), d_stats, stats.size() * 8, hipMemcpyDeviceToHost, st));
-    }
-    SYBL_HIP(hipStreamSynchronize(st));  // the ONE wait for the statistics of every block of every column
-
-    // ---- set columns: the host CSR over the output's physical rows, gathered from the permutation
-    bool any_set = false;
-    for (auto &cp : t->cols) any_set = any_set || cp->type == SYBL_SET_VAL;
-    if (any_set) {
-        std::vector<uint32_t> hperm((size_t)N);
-        SYBL_HIP(hipMemcpy(hperm.data(), perm, (size_t)N * 4, hipMemcpyDeviceToHost));
-        for (size_t k = 0; k < nc; k++) {
-            const Column *c = t->cols[k].get();
-            Column *n = o->cols[k].get();
-            if (c->type != SYBL_SET_VAL) continue;
-            n->h_set_off.assign(1, 0);
-            n->h_set_off.reserve((size_t)phys_out + 1);
-            for (int64_t j = 0; j < nb_out; j++) {
-                const int64_t rows = j + 1 < nb_out ? stride : last_n;  // (padding rows: empty sets; the table ends with its last row)
-                for (int64_t r = 0; r < rows; r++) {
-                    const int64_t i = j * block_rows + r;
-                    if (r < block_rows && i < N) {
-                        const size_t s = hperm[(size_t)i];
-                        if (s + 1 < c->h_set_off.size())
-                            n->h_set_vals.insert(n->h_set_vals.end(), c->h_set_vals.begin() + c->h_set_off[s], c->h_set_vals.begin() + c->h_set_off[s + 1]);
-                    }
-                    n->h_set_off.push_back((int64_t)n->h_set_vals.size());
-                }
-            }
-            n->set_dirty = true;
-        }
-    }
-
-    // ---- the block writer: segments, block statistics, versions.  Nothing here waits for the GPU.
-    for (int64_t j = 0; j < nb_out; j++) {
-        const Segment &sg = osegs[(size_t)j];
-        BlockWriter w;
-        if ((rc = block_begin(o, sg.n, &w))) return rc;
-        if (w.start != sg.start) return fail(SYBL_E_STATE, "digest: block %lld begins at row %lld, not %lld", (long long)j, (long long)w.start, (long long)sg.start);
-        for (size_t k = 0; k < nc; k++) {
-            Column *n = o->cols[k].get();
-            void *col = nullptr;
-            uint32_t *valid = nullptr;
-            // all_populated: the writer leaves the rows alone (they are in place) and sets the block's validity words, if the
-            // column has any, to ones -- the gathered words replace them below
-            bool direct = false;
-            if (want_stats && n->type != SYBL_SET_VAL) {
-                const int64_t *h = stats.data() + k * 3 * (size_t)nb_out;
-                const int64_t mn = h[j], mx = h[nb_out + j], pop = h[2 * nb_out + j];
-                if ((rc = block_col_direct(w, n, true, mn, mx, pop, &col, &valid, &direct))) return rc;
-                if (!direct) {
-                    // (SYBL_NO_DIRECT_DECODE: through the staging block -- the rows in place, decoded, and packed back at commit)
-                    if ((rc = block_col_device(w, n, true, &col, &valid))) return rc;
-                    hipError_t e = launch_repack((const char *)n->d_data + (size_t)sg.start * (size_t)n->elem, n->elem, n->vbase, col, n->canon(), 0, sg.n, st);
-                    if (e != hipSuccess) return hip_fail(e, "k_repack");
-                    block_col_stats(w, n, mn, mx, pop);
-                    continue;
-                }
-            } else if ((rc = block_col_device(w, n, true, &col, &valid))) {
-                return rc;
-            }
-            if (n->type != SYBL_SET_VAL && col != (char *)n->d_data + (size_t)sg.start * (size_t)n->elem)
-                return fail(SYBL_E_STATE, "digest: column '%s' moved under the writer", n->name.c_str());
-        }
-        if ((rc = block_commit(w))) return rc;
-    }
-    for (size_t k = 0; k < nc; k++) {
-        Column *n = o->cols[k].get();
-        if (!vbits[k]) continue;
-        SYBL_HIP(hipMemcpyAsync(n->d_valid, vbits[k], (size_t)n_words * 4, hipMemcpyDeviceToDevice, st));
-        n->has_missing = n->has_missing || t->cols[k]->has_missing;
-    }
-    SYBL_HIP(hipStreamSynchronize(st));
+    // ---- gather, statistics, set columns, the block writer (gather_rows below)
+    if ((rc = gather_rows(t, src, perm, N, block_rows, o, pool, "digest", &ev[3], &S->gather_bytes, &S->blocks))) return rc;
     float ms[3] = {0, 0, 0};
     for (int k = 0; k < 3; k++) SYBL_HIP(hipEventElapsedTime(&ms[k], ev[k], ev[k + 1]));
     S->keys_ms = ms[0];
     S->sort_ms = ms[1];
     S->gather_ms = ms[2];
-    S->blocks = nb_out;
     S->keys_bytes = N * ((int64_t)tc->elem + (int64_t)ksz + 4);
     // (an LSD pass per 8 bits reads and writes every pair; the histogram pass reads the keys once more)
     S->sort_bytes = (int64_t)((bits + 7) / 8) * 2 * N * ((int64_t)ksz + 4) + N * (int64_t)ksz;

@@ -28,6 +28,7 @@
 #include <algorithm>
 #include <new>
 
+#include "bitmap_rank.h"
 #include "engine.h"
 
 namespace sybl {
@@ -37,18 +38,11 @@ namespace sybl {
 // not needle-in-haystack) are answered inside it.
 constexpr int kSmpFirstWindow = 16;
 constexpr int kSmpWindowGrowth = 4;
-constexpr int kSmpThreads = 256;           // k_smp_count / k_smp_compact: four waves, a 32-bit bitmap word per lane
 constexpr int kSmpPrefixThreads = 1024;
 constexpr int kSmpMaxFilterCols = 8;       // k_prefilter is instantiated for 1..8 slots
 
 // device state of one query: int64 words
 enum { kSmpTotal = 0, kSmpDone = 1, kSmpP = 2, kSmpM = 3, kSmpStateWords = 4 };
-
-struct SmpBlock {
-    int64_t start;  // first physical row (a multiple of 32)
-    int64_t n;      // logical rows
-    int64_t lbase;  // table-wide logical index of the block's first row
-};
 
 // a column as the compaction (order key) and gather kernels read it
 struct SmpCol {
@@ -74,42 +68,9 @@ __device__ __forceinline__ bool smp_valid(const uint32_t *valid, int64_t row) {
     return valid == nullptr || ((valid[row >> 5] >> (row & 31)) & 1u);
 }
 
-// word i of a block of n rows: its bitmap word (every row when there is no bitmap), rows beyond n masked off
-__device__ __forceinline__ uint32_t smp_word(const uint32_t *bits, int64_t w0, int64_t i, int64_t n) {
-    uint32_t w = bits ? bits[w0 + i] : 0xFFFFFFFFu;
-    const int64_t left = n - i * 32;
-    if (left < 32) w &= (1u << (uint32_t)left) - 1u;
-    return w;
-}
-
-// inclusive scan over the 64 lanes of a wave
-template <typename T>
-__device__ __forceinline__ T wave_scan_incl(T v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const T u = __shfl_up(v, o, 64);
-        if (lane >= o) v += u;
-    }
-    return v;
-}
-
-// ---- m_b: a workgroup per block, lanes take 32-bit words, one store per block.  bits is indexed from word `word0`.
+// ---- m_b (bitmap_rank.h: the block descriptor, smp_word, wave_scan_incl and the count are shared with select.hip)
 __global__ __launch_bounds__(kSmpThreads) void k_smp_count(const uint32_t *bits, int64_t word0, const SmpBlock *blk, int64_t *cnt) {
-    __shared__ int64_t part[kSmpThreads / 64];
-    const SmpBlock B = blk[blockIdx.x];
-    const int64_t words = (B.n + 31) >> 5, w0 = (B.start >> 5) - word0;
-    int64_t c = 0;
-    for (int64_t i = threadIdx.x; i < words; i += kSmpThreads) c += __popc(smp_word(bits, w0, i, B.n));
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        int64_t s = 0;
-        for (int w = 0; w < kSmpThreads / 64; w++) s += part[w];
-        cnt[blockIdx.x] = s;
-    }
+    smp_count_block(bits, word0, blk, cnt);
 }
 
 // ---- exclusive scan of the window's m_b (excl[b] = matching rows before block b, table-wide), continuing from the windows

@@ -303,6 +303,26 @@ class Table:
         finally:
             N.lib().sybl_samples_free(h)
 
+    def select(self, filters=(), columns=None, block_rows=0):
+        """The rows that pass every filter, in table order, cut into blocks of block_rows (0 = 65536), as a NEW resident table
+        holding `columns` (None = every column) in the order named (sybl_table_select).  This table is untouched; free both."""
+        keep = []
+        d = N.SelectDesc()
+        d.n_filters, d.filters = len(filters), C.cast(self._filter_array(filters, keep), C.POINTER(N.Filter))
+        names = [_b(c) for c in columns] if columns is not None else []
+        carr = (C.c_char_p * max(len(names), 1))(*names)
+        d.n_columns, d.columns = len(names), (C.cast(carr, C.POINTER(C.c_char_p)) if names else None)
+        d.block_rows = block_rows
+        h = C.c_void_p()
+        N.check(N.lib().sybl_table_select(self._h, C.byref(d), C.byref(h)))
+        return Table(self.ctx, h, self.name)
+
+    def select_stats(self):
+        """Device time and bytes of the phases of the select() that made this table (sybl_table_select_stats)."""
+        st = N.SelectStats()
+        N.check(N.lib().sybl_table_select_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
     def query(self, filters=(), groups=(), aggs=(), op="avg", hist_bucket=0, want_percentiles=True, time_col=None,
               time_bucket=0, weight_col=None, order_by="$COUNT", order_asc=False, limit=0, block_skip=False, loghist=False, str_replace=(),
               distincts=(), printed_only=False):
