@@ -116,6 +116,8 @@ static void free_query(Query *q) {
     if (q->d_prebits) hipFree(q->d_prebits);
     if (q->d_segs) hipFree(q->d_segs);
     if (q->d_wg_seg_begin) hipFree(q->d_wg_seg_begin);
+    if (q->d_pieces) hipFree(q->d_pieces);
+    if (q->d_piece_queue) hipFree(q->d_piece_queue);
     if (q->d_wg_cell_base) hipFree(q->d_wg_cell_base);
     if (q->d_recs) hipFree(q->d_recs);
     if (q->d_h32) hipFree(q->d_h32);
@@ -226,6 +228,32 @@ static int out_log_end(Query *q, bool ran, hipStream_t st) {
     if (!q->d_out_stage || !ran) return SYBL_OK;
     hipError_t e = launch_outlog_gather(q->d_out_stage, q->out_cap, q->d_out_log, q->d_sum, st);
     if (e != hipSuccess) return hip_fail(e, "k_outlog_gather");
+    return SYBL_OK;
+}
+
+// SYBL_WG_CLOCKS=1: one line on stderr -- the workgroups' exit times (us after the first workgroup entered its loop; wall_clock64()
+// ticks at 100 MHz), and how far the last one finished behind the median as a share of the kernel.
+static int report_wg_clocks(const void *d_clock, int n_wg, hipStream_t st) {
+    std::vector<unsigned long long> c((size_t)n_wg * 2);
+    SYBL_HIP(hipStreamSynchronize(st));
+    SYBL_HIP(hipMemcpy(c.data(), d_clock, c.size() * 8, hipMemcpyDeviceToHost));
+    unsigned long long first = ~0ull;
+    std::vector<double> in, out;
+    for (int w = 0; w < n_wg; w++) {
+        if (!c[(size_t)2 * w]) continue;  // (a workgroup that wrote nothing)
+        first = std::min(first, c[(size_t)2 * w]);
+    }
+    for (int w = 0; w < n_wg; w++) {
+        if (!c[(size_t)2 * w]) continue;
+        in.push_back((double)(c[(size_t)2 * w] - first) / 100.0);
+        out.push_back((double)(c[(size_t)2 * w + 1] - first) / 100.0);
+    }
+    if (out.empty()) return SYBL_OK;
+    std::sort(in.begin(), in.end());
+    std::sort(out.begin(), out.end());
+    const double lo = out.front(), med = out[out.size() / 2], hi = out.back();
+    fprintf(stderr, "wg clocks: n=%zu entry_max=%.1f exit_min=%.1f exit_med=%.1f exit_max=%.1f us, (max-med)/kernel=%.2f%% (max-min)/kernel=%.2f%%\n",
+            out.size(), in.back(), lo, med, hi, hi > 0 ? 100.0 * (hi - med) / hi : 0.0, hi > 0 ? 100.0 * (hi - lo) / hi : 0.0);
     return SYBL_OK;
 }
 
@@ -443,7 +471,20 @@ static int scan(Query *q) {
             if (q->fast_packed_n) {
                 e = launch_scan_packed_n(q->fplan, q->fast_nf, q->fast_ng, q->fast_na, q->fast_mode, q->time_mode, q->n_wg, q->lds_bytes, st);
             } else if (q->fast_packed) {
+                // SYBL_WG_CLOCKS=1 (diagnostic): when every workgroup of k_scan_packed entered and left its loop
+                DevOwner own_clock;
+                q->fplan.wg_clock = nullptr;
+                if (env("SYBL_WG_CLOCKS")) {
+                    SYBL_HIP(hipMalloc(&own_clock.p, (size_t)q->n_wg * 16));
+                    SYBL_HIP(hipMemsetAsync(own_clock.p, 0, (size_t)q->n_wg * 16, st));
+                    q->fplan.wg_clock = (unsigned long long *)own_clock.p;
+                }
+                if (q->fplan.dyn) SYBL_HIP(hipMemsetAsync(q->d_piece_queue, 0, 4, st));  // the next piece's index
                 e = launch_scan_packed(q->fplan, q->fast_nf, q->fast_ng, q->fast_na, q->fast_mode, q->time_mode, q->n_wg, q->lds_bytes, st);
+                if (e == hipSuccess && own_clock.p) {
+                    q->fplan.wg_clock = nullptr;
+                    if ((rc = report_wg_clocks(own_clock.p, q->n_wg, st))) return rc;
+                }
             } else {
                 e = launch_scan_fast(q->fplan, q->fast_nf, q->fast_ng, q->fast_na, q->fast_mode, q->time_mode, q->fast_gen, q->n_wg,
                                      q->lds_bytes, st);

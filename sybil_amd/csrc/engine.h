@@ -429,6 +429,13 @@ struct Query {
     std::vector<int32_t> wg_seg_begin;
     Segment *d_segs = nullptr;
     int32_t *d_wg_seg_begin = nullptr;
+    // dynamic dealing (FastPlan::dyn; planner.cpp: plan_dynamic): the table's pieces and the queue word k_scan_packed draws from
+    bool dyn = false;
+    int piece_tiles = 0;
+    int32_t piece_cap = 0;
+    std::vector<Piece> pieces;
+    Piece *d_pieces = nullptr;
+    uint32_t *d_piece_queue = nullptr;
     int32_t *d_wg_cell_base = nullptr;
     std::vector<void *> d_idmasks;
     int64_t n_sum_words = 0, n_max_words = 0;

@@ -1511,7 +1511,7 @@ struct Planner {
 
     int work() {
         // ---- work: non-skipped blocks -> runs of physical rows -> an equal share of tiles per workgroup
-        std::vector<Segment> runs;
+        runs.clear();
         rows_scanned = 0;
         skipped = 0;
         for (size_t b = 0; b < t->blocks.size(); b++) {
@@ -1532,8 +1532,13 @@ struct Planner {
         return SYBL_OK;
     }
 
-    // the most rows one lane of k_scan_packed sees: four of every tile of its workgroup
+    std::vector<Segment> runs;  // work(): the rows to scan, in table order
+    bool quiet = false;         // plan_dynamic(): a trial run of the proofs -- no SYBL_PLAN_TRACE line
+
+    // the most rows one lane of k_scan_packed sees: four of every tile of its workgroup (dynamic dealing: of every tile a
+    // workgroup can receive under its cap -- whole pieces)
     int64_t max_lane_rows() const {
+        if (q->dyn) return (int64_t)q->piece_cap * q->piece_tiles * kPackedRows;
         int64_t lane_rows = 0;
         for (int w = 0; w < q->n_wg; w++) {
             int64_t mine = 0;
@@ -1567,7 +1572,7 @@ struct Planner {
         const int sum_bits = std::max(1, bits(umax * slot_rows)), count_bits = bits(slot_rows);
         if (sum_bits + count_bits <= 64 && sum_bits < 63) FP.cshift = sum_bits;
         // SYBL_PLAN_TRACE=1 (diagnostic): the decision and the widths behind it, also when they do not fit (cshift=0)
-        if (env("SYBL_PLAN_TRACE"))
+        if (env("SYBL_PLAN_TRACE") && !quiet)
             fprintf(stderr, "count packing: cshift=%d sum_bits=%d count_bits=%d slot_rows=%lld\n", (int)FP.cshift, sum_bits, count_bits, (long long)slot_rows);
     }
 
@@ -1609,7 +1614,7 @@ struct Planner {
         }
         if (digits && mul24) FP.lean |= (int32_t)kLeanProved;
         if (q->fast_mode != kFastMoments) {
-            if (env("SYBL_PLAN_TRACE")) fprintf(stderr, "lean hist: proved=%d digits=%d mul24=%d\n", (FP.lean & (int32_t)kLeanProved) ? 1 : 0, (int)digits, (int)mul24);
+            if (env("SYBL_PLAN_TRACE") && !quiet) fprintf(stderr, "lean hist: proved=%d digits=%d mul24=%d\n", (FP.lean & (int32_t)kLeanProved) ? 1 : 0, (int)digits, (int)mul24);
             return;
         }
         // -- kLeanMoments
@@ -1645,7 +1650,7 @@ struct Planner {
             FP.rep_shift = rs;
             q->lds_bytes = ((size_t)words_lean * (size_t)P.lds_cells * 8) << rs;
         }
-        if (env("SYBL_PLAN_TRACE")) {
+        if (env("SYBL_PLAN_TRACE") && !quiet) {
             fprintf(stderr, "lean moments: lean=%d proved=%d digits=%d mul24=%d cshift=%d count_bits=%d", cshift ? 1 : 0, (FP.lean & (int32_t)kLeanProved) ? 1 : 0,
                     (int)digits, (int)mul24, cshift, lean_bits(slot_rows));
             for (int a = 0; a < na && shape; a++)
@@ -1654,6 +1659,60 @@ struct Planner {
             fprintf(stderr, " slot_rows=%lld tried_replicas=%d words=%d replicas=%d\n", (long long)slot_rows, 1 << rs, cshift ? words_lean : words_now,
                     1 << P.rep_shift);
         }
+    }
+
+    // FastPlan::dyn (scan_packed.h: packed_scan_dyn): the plain, non-windowed k_scan_packed takes the table's pieces from a device
+    // queue instead of one contiguous share per workgroup.  Taken when a workgroup's share is at least SYBL_DYN_MIN_TILES tiles
+    // (default 128: below that the table is a few pieces per workgroup and the shares are what balance it) and the packing
+    // proofs hold for the most rows a workgroup can then receive (max_lane_rows under the cap): a plan that would lose cshift
+    // or the lean layout to the cap stays static and keeps them.  The proofs run quietly for both dealings and once more,
+    // traced, for the one taken; each run starts from the replica count and table size strategy() chose.
+    // SYBL_NO_DYN=1: static.  SYBL_DYN=1: the plain loop too.  SYBL_DYN_PIECE_TILES: tiles per piece (default 32).  SYBL_DYN_CAP_PCT (tests): the cap's share.
+    void plan_dynamic() {
+        FastPlan &FP = q->fplan;
+        const int32_t rep_shift0 = P.rep_shift, fp_rep_shift0 = FP.rep_shift;
+        const size_t lds_bytes0 = q->lds_bytes;
+        auto proofs = [&](bool dyn, bool silent) {
+            P.rep_shift = rep_shift0;
+            FP.rep_shift = fp_rep_shift0;
+            q->lds_bytes = lds_bytes0;
+            q->dyn = dyn;
+            quiet = silent;
+            plan_count_packing();
+            plan_lean();
+            quiet = false;
+        };
+        q->dyn = false;
+        q->pieces.clear();
+        q->piece_tiles = kPieceTilesDefault;
+        if (const char *e = env("SYBL_DYN_PIECE_TILES")) q->piece_tiles = std::min(std::max(atoi(e), 1), kPieceTilesMax);
+        int64_t min_tiles = 128, total_tiles = 0;
+        if (const char *e = env("SYBL_DYN_MIN_TILES")) min_tiles = std::max<int64_t>(atoll(e), 1);
+        for (auto &r : runs) total_tiles += (r.n + kPackedTileRows - 1) / kPackedTileRows;
+        // (the loop the kernel will run: scan_packed.h.  Only the late-materialisation loop takes the queue by default -- the
+        // plain one-tile-ahead loop measured no faster with it, see DESIGN 3.0 -- SYBL_DYN=1 opts the plain loop in)
+        const bool late_loop = kPackedLate && q->fast_nf > 0 && q->fast_ng + q->fast_na + (q->time_mode ? 1 : 0) > 0;
+        bool want = q->fast && q->fast_packed && !q->fast_packed_n && !q->hash_mode && !q->part_hist && q->use_lds && !P.windowed && !FP.nul &&
+                    !q->pre_n_slots && !env("SYBL_NO_DYN") && !env("SYBL_PACKED_RING") && (late_loop || env("SYBL_DYN")) && (total_tiles + std::max(q->n_wg, 1) - 1) / std::max(q->n_wg, 1) >= min_tiles;
+        if (want) {
+            deal_pieces(runs, q->piece_tiles, q->pieces);
+            int64_t pct = kPieceCapPct;
+            if (const char *e = env("SYBL_DYN_CAP_PCT")) pct = atoll(e);
+            q->piece_cap = (int32_t)std::min<int64_t>(piece_cap((int64_t)q->pieces.size(), q->n_wg, pct), INT32_MAX);
+            want = !q->pieces.empty() && q->pieces.size() < ((size_t)1 << 30);
+        }
+        if (want) {
+            proofs(false, true);
+            const int32_t cshift_static = FP.cshift, lean_static = FP.lean;
+            proofs(true, true);
+            const bool avg = q->fast_mode == kFastAvg || q->fast_mode == kFastAvgMax;
+            if ((avg && cshift_static && !FP.cshift) || ((lean_static & (int32_t)kLeanMoments) && !(FP.lean & (int32_t)kLeanMoments))) want = false;
+        }
+        proofs(want, false);
+        if (!want) q->pieces.clear();
+        if (env("SYBL_PLAN_TRACE") && q->fast && q->fast_packed)
+            fprintf(stderr, "dealing: dynamic=%d pieces=%zu piece_tiles=%d cap=%d lane_rows=%lld\n", want ? 1 : 0, q->pieces.size(), q->piece_tiles,
+                    want ? q->piece_cap : 0, (long long)max_lane_rows());
     }
 
     // -limit pushed into the scan (pushdown.hip).  Taken when the caller said the rows beyond the limit need nothing but their
@@ -1773,8 +1832,7 @@ struct Planner {
         select_hash_fast(t, q, slot_col);
         prefilter_commit();
         if ((rc = select_part_hist(t, q, slot_col, rows_scanned))) return rc;
-        plan_count_packing();
-        plan_lean();
+        plan_dynamic();  // (plan_count_packing and plan_lean, for the dealing it takes)
         if ((rc = plan_pushdown())) return rc;
         q->stats.rows_scanned = rows_scanned;
         q->stats.blocks_skipped = skipped;
@@ -1829,6 +1887,20 @@ struct Planner {
         }
         q->fplan.segs = q->d_segs;
         q->fplan.wg_seg_begin = q->d_wg_seg_begin;
+        q->fplan.dyn = 0;
+        if (q->dyn) {
+            // the piece table, like segs; the queue is one word of its own (d_sum's header is the all-reduce payload) that
+            // every scan zeroes on its stream in front of the kernel
+            SYBL_HIP(hipMalloc((void **)&q->d_pieces, q->pieces.size() * sizeof(Piece)));
+            SYBL_HIP(hipMemcpy(q->d_pieces, q->pieces.data(), q->pieces.size() * sizeof(Piece), hipMemcpyHostToDevice));
+            SYBL_HIP(hipMalloc((void **)&q->d_piece_queue, 64));
+            SYBL_HIP(hipMemset(q->d_piece_queue, 0, 64));
+            q->fplan.dyn = 1;
+            q->fplan.pieces = q->d_pieces;
+            q->fplan.n_pieces = (int32_t)q->pieces.size();
+            q->fplan.piece_cap = q->piece_cap;
+            q->fplan.piece_queue = q->d_piece_queue;
+        }
         q->fplan.ws_sum = q->d_ws_sum;
         q->fplan.ws_max = q->d_ws_max;
         if (!q->h_multi.empty()) {

@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include "plan.h"
+#include "pieces.h"
 #include "outlog.h"
 #include "wg_header.h"
 
@@ -118,6 +119,14 @@ struct FastPlan {
     int64_t *sum_out, *max_out, *ws_sum, *ws_max;
     const Segment *segs;
     const int32_t *wg_seg_begin;
+    // SYBL_WG_CLOCKS=1 (diagnostic, k_scan_packed): wall_clock64() at every workgroup's loop entry and loop exit, two words per
+    // workgroup; nullptr = not kept
+    unsigned long long *wg_clock;
+    // k_scan_packed, dynamic dealing (pieces.h; planner.cpp: plan_dynamic): the workgroups take the table's pieces from
+    // *piece_queue (zero when the kernel starts) instead of scanning segs[wg_seg_begin[w] ..]; at most piece_cap tickets each
+    int32_t dyn, n_pieces, piece_cap;
+    const Piece *pieces;
+    uint32_t *piece_queue;
 };
 
 hipError_t launch_scan_fast(const FastPlan &P, int nf, int ng, int na, int mode, bool time, bool gen, int n_wg,

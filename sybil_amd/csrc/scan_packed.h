@@ -468,12 +468,217 @@ constexpr bool kPackedLateBranch = SYBL_PACKED_LATE_BRANCH != 0;
 #ifndef SYBL_PACKED_WAVES_PER_EU
 #define SYBL_PACKED_WAVES_PER_EU 4
 #endif
+
+// ---- dynamic dealing (FastPlan::dyn; pieces.h) ----------------------------------------------------------------------------
+// The loops of k_scan_packed without NUL over the workgroup's sequence of TILES across the pieces it draws, instead of over its
+// share of segments.  A tile is the 64-bit physical row of its first row and its number of rows (1 .. 4096; 0 = past the
+// workgroup's last piece: descriptors of zero records, rows that fail `k < left`); both are wave-uniform, and the descriptor of
+// a column is (column + (R + the wave's row) * width, the wave's rows * width) -- the static loops' per-tile 64-bit add with R
+// in place of the chunk's first row plus the row inside it.  Nothing drains at a piece's end: the loops below never see pieces.
+static_assert(kPackedTileRows == kPieceTileRows, "pieces.h counts k_scan_packed's tiles");
+struct DynTile {
+    int64_t R;
+    uint32_t rows;
+};
+constexpr uint32_t kNoTicket = 0xFFFFFFFFu;
+
+// The workgroup's cursor over its pieces.  Thread 0 draws the tickets -- one returning agent-scope increment each, ONE piece
+// ahead of the piece being entered, so the atomic's latency is a piece long in the past when its value is wanted -- and hands
+// them to the other waves through a ring of LDS words and the one barrier a piece costs.  Every decision below is taken from
+// those words, so it is the same in all 16 waves: they enter the same pieces, meet at the same barriers and leave together.  A
+// workgroup never waits for another one (no flag, no spinning): it cannot hang.  (piece_cap, pieces.h: why every piece is
+// scanned exactly once.)
+// (The increment is atomic_inc with a bound of 2^32 - 1, not fetch_add: the compiler rewrites a fetch_add into a wave-wide
+// reduction whose result it waits for on the spot -- s_waitcnt vmcnt(0) right behind the atomic.  The piece itself is read
+// through the constant address space: one scalar 16-byte load, counted apart from the vector loads.)
+static_assert(sizeof(Piece) == 16 && offsetof(Piece, start) == 0 && offsetof(Piece, n) == 8, "enter_piece reads a piece as four dwords");
+struct DynCursor {
+    const FastPlan &P;
+    uint32_t *ring;          // LDS, 4 words: ring[k & 3] = the ticket of the k-th piece this workgroup enters
+    uint32_t k = 0;          // pieces entered
+    int64_t R = 0;           // next tile's first row
+    uint32_t left = 0;       // rows of the entered piece not yet handed out
+    bool done = false;       // a ticket past the table (or the cap): no more pieces
+    uint32_t pend = kNoTicket, drawn = 0;  // (thread 0) the ticket drawn ahead; tickets drawn
+    bool pend_ok = false;                  // (thread 0) ... and whether one was drawn at all
+    bool want_draw = false;                // (thread 0) the next ticket is still to be drawn: draw_ahead()
+
+    __device__ __forceinline__ DynCursor(const FastPlan &P_, uint32_t *ring_) : P(P_), ring(ring_) {
+        if (threadIdx.x == 0) {
+            draw();
+            ring[0] = pend_ok ? pend : kNoTicket;
+            draw();
+        }
+        __syncthreads();
+    }
+    __device__ __forceinline__ void draw() {
+        pend_ok = drawn < (uint32_t)P.piece_cap;
+        if (pend_ok) {
+            pend = __builtin_amdgcn_atomic_inc32(P.piece_queue, 0xFFFFFFFFu, __ATOMIC_RELAXED, "agent");
+            drawn++;
+        }
+    }
+    // Called where the loops have just waited for their youngest loads (the decode of a tile): waiting for `pend` there
+    // holds no load back.  ring[(k + 1) & 3] was last read when piece k - 3 was entered, three barriers ago.
+    __device__ __forceinline__ void enter_piece() {
+        if (threadIdx.x == 0) {
+            if (want_draw) draw();  // (two pieces entered within one iteration: the draw has had no chance yet)
+            const uint32_t ahead = pend_ok ? pend : kNoTicket;
+            if (ahead >= (uint32_t)P.n_pieces) drawn = (uint32_t)P.piece_cap;  // the table has been dealt: draw no more
+            ring[(k + 1) & 3u] = ahead;
+            want_draw = true;
+        }
+        __syncthreads();
+        const uint32_t ticket = __builtin_amdgcn_readfirstlane(ring[k & 3u]);
+        k++;
+        const bool have = ticket < (uint32_t)P.n_pieces;  // (the table read is bounded here; n_pieces >= 1)
+        typedef const __attribute__((address_space(4))) pu32x4 *piece_words;
+        const pu32x4 pc = *(piece_words)(uintptr_t)(P.pieces + (have ? ticket : 0u));
+        R = (int64_t)(((uint64_t)pc.y << 32) | pc.x);
+        left = have ? pc.z : 0u;
+        done = !have;
+    }
+    // The draw that entering a piece asks for, issued BEHIND the iteration's loads: in front of them its return would be waited
+    // for before they are issued (the compiler's next vmcnt(0)); behind them it comes back with them.
+    __device__ __forceinline__ void draw_ahead() {
+        if (threadIdx.x == 0 && want_draw) {
+            draw();
+            want_draw = false;
+        }
+    }
+    __device__ __forceinline__ DynTile next() {
+        if (left == 0 && !done) enter_piece();
+        DynTile T;
+        T.R = ((int64_t)__builtin_amdgcn_readfirstlane((int)(R >> 32)) << 32) | (uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)R);
+        left = __builtin_amdgcn_readfirstlane(left);
+        T.rows = left < (uint32_t)kPackedTileRows ? left : (uint32_t)kPackedTileRows;
+        R = T.R + kPackedTileRows;
+        left -= T.rows;
+        return T;
+    }
+};
+
+template <int NF, int NG, int NA, int MODE, bool TIME, bool G1, int LEANV>
+__device__ __forceinline__ void packed_scan_dyn(const FastPlan &P, int64_t *lds, const FastLds &L, const bool max32, uint32_t &matched,
+                                                uint32_t &overflow) {
+    __shared__ uint32_t ring[4];
+    const uint32_t tid = threadIdx.x;
+    const uint32_t wave_row = __builtin_amdgcn_readfirstlane((tid & ~63u) * kPackedRows);  // the wave's first row inside a tile
+    const uint32_t lane_row = (tid & 63u) * kPackedRows;                                  // the lane's inside the wave's 256
+    DynCursor cur(P, ring);
+    PackedRaw<NF> rf;
+    PackedRaw<NG> rg;
+    PackedRaw<NA> ra;
+    PackedRaw<1> rt;
+    PackedTile<NF> f;
+    PackedTile<NG> g;
+    PackedTile<NA> a;
+    PackedTile<1> t;
+    // one column's four rows for this lane: whole lanes up to the tile's end, like packed_issue_ring (`wanted` false, wave-
+    // uniform: a descriptor of zero records -- the range check answers without touching memory)
+    auto issue = [&](const void *col, int width, const DynTile &T, bool wanted, pu32x4 &raw, bool one_dword) {
+        const uint32_t rows = wanted && T.rows > wave_row
+                                  ? (T.rows - wave_row < 64u * kPackedRows ? (T.rows - wave_row + kPackedRows - 1) & ~(uint32_t)(kPackedRows - 1) : 64u * kPackedRows)
+                                  : 0u;
+        const int64_t base = rows ? T.R + wave_row : 0;
+        const int ws = width >> 1;  // width 1, 2, 4 -> shift 0, 1, 2
+        const __amdgpu_buffer_rsrc_t rsrc =
+            __builtin_amdgcn_make_buffer_rsrc((void *)((const uint8_t *)col + ((size_t)base << ws)), 0, (int)(rows << ws), (int)kBufferRsrcWord3);
+        if (one_dword) raw.x = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)lane_row, 0, 2);  // (G1: width 1, see packed_issue1)
+        else raw = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(lane_row << ws), 0, 2);     // aux 2 = nt: streamed once
+    };
+    auto issue_filters = [&](const DynTile &T) {
+#pragma unroll
+        for (int c = 0; c < NF; c++) issue(P.fcol[c], P.fwid[c], T, true, rf.v[c], false);
+    };
+    auto issue_rest = [&](const DynTile &T, bool wanted) {
+        if (TIME) issue(P.tcol, P.twid, T, wanted, rt.v[0], false);
+#pragma unroll
+        for (int c = 0; c < NG; c++) issue(P.gcol[c], G1 ? 1 : P.gwid[c], T, wanted, rg.v[c], G1);
+#pragma unroll
+        for (int c = 0; c < NA; c++) issue(P.acol[c], P.awid[c], T, wanted, ra.v[c], false);
+    };
+    auto decode_rest = [&]() {
+        if (TIME) packed_decode(P.twid, rt.v[0], t.u[0]);
+#pragma unroll
+        for (int c = 0; c < NG; c++) packed_decode(G1 ? 1 : P.gwid[c], rg.v[c], g.u[c]);
+#pragma unroll
+        for (int c = 0; c < NA; c++) packed_decode(P.awid[c], ra.v[c], a.u[c]);
+    };
+    auto lane_left = [&](const DynTile &T) -> uint32_t { return T.rows > tid * kPackedRows ? T.rows - tid * kPackedRows : 0u; };
+    if (kPackedLate && NF > 0 && NG + NA + (TIME ? 1 : 0) > 0) {
+        // late materialisation as in k_scan_packed's static loop: filters of tile t + 2 and keys / values of t + 1 in flight
+        // while the rows of t are consumed
+        PackedTile<0> f0;
+        auto filter_bits = [&](const DynTile &T) -> uint32_t {
+#pragma unroll
+            for (int c = 0; c < NF; c++) packed_decode(P.fwid[c], rf.v[c], f.u[c]);
+            const uint32_t left = lane_left(T);
+            uint32_t bits = 0;
+#pragma unroll
+            for (int k = 0; k < kPackedRows; k++) {
+                bool pass = (uint32_t)k < left;
+#pragma unroll
+                for (int c = 0; c < NF; c++) pass = pass & (f.u[c][k] >= P.plo[c]) & (f.u[c][k] <= P.phi[c]);
+                bits |= pass ? 1u << k : 0u;
+            }
+            return bits;
+        };
+        DynTile T0 = cur.next();
+        issue_filters(T0);
+        uint32_t bits = filter_bits(T0);
+        DynTile T1 = cur.next();
+        issue_rest(T0, __builtin_amdgcn_ballot_w64(bits != 0) != 0);
+        issue_filters(T1);
+        cur.draw_ahead();
+        while (T0.rows) {
+            decode_rest();  // keys / values / time of T0 (zeros if nothing was wanted)
+            const uint32_t next_bits = filter_bits(T1);
+            const DynTile T2 = cur.next();  // (every load issued so far has been waited for)
+            if (kPackedLateBranch) {
+                if (__builtin_amdgcn_ballot_w64(next_bits != 0) != 0) issue_rest(T1, true);
+            } else {
+                issue_rest(T1, __builtin_amdgcn_ballot_w64(next_bits != 0) != 0);
+            }
+            issue_filters(T2);
+            cur.draw_ahead();
+            matched += (uint32_t)__builtin_popcount(bits);
+            packed_plain_tile<0, NG, NA, MODE, TIME, false, true, LEANV>(P, f0, g, a, t, [&](int k) -> bool { return (bits >> k) & 1u; }, lds, L, max32,
+                                                                         matched, overflow);
+            bits = next_bits;
+            T0 = T1;
+            T1 = T2;
+        }
+        return;
+    }
+    // the plain loop: every column of tile t + 1 in flight while the rows of t are consumed
+    DynTile T0 = cur.next();
+    issue_filters(T0);
+    issue_rest(T0, true);
+    cur.draw_ahead();
+    while (T0.rows) {
+#pragma unroll
+        for (int c = 0; c < NF; c++) packed_decode(P.fwid[c], rf.v[c], f.u[c]);
+        decode_rest();
+        const DynTile T1 = cur.next();  // (every load issued so far has been waited for)
+        issue_filters(T1);
+        issue_rest(T1, true);
+        cur.draw_ahead();
+        const uint32_t left = lane_left(T0);
+        if (NF == 0) matched += left < (uint32_t)kPackedRows ? left : (uint32_t)kPackedRows;  // no filter: every row of the tile
+        packed_plain_tile<NF, NG, NA, MODE, TIME, false, NF == 0, LEANV>(P, f, g, a, t, [&](int k) { return (uint32_t)k < left; }, lds, L, max32,
+                                                                        matched, overflow);
+        T0 = T1;
+    }
+}
 // LEANV: what the planner proved for this launch (FastPlan::lean: kLeanMoments | kLeanProved) as a property of the KERNEL -- the
 // launcher picks the instantiation, and a lean kernel holds the lean body only.  (Two bodies chosen per tile inside one loop
 // cost the loop 20 more spilled scalar registers; DESIGN 3.6 has the same finding for two loops in one kernel.)
-template <int NF, int NG, int NA, int MODE, bool TIME, bool G1, bool NUL, int RING = 0, int LEANV = 0>
+// DYN: FastPlan::dyn, likewise a property of the kernel -- the dynamic loops instead of the static ones (packed_scan_dyn).
+template <int NF, int NG, int NA, int MODE, bool TIME, bool G1, bool NUL, int RING = 0, int LEANV = 0, bool DYN = false>
 __global__ __launch_bounds__(kWgThreads, SYBL_PACKED_WAVES_PER_EU) void k_scan_packed(const FastPlan P) {
     static_assert(LEANV == 0 || !NUL, "the NUL kernels mix row bodies: no proofs");
+    static_assert(!DYN || (!NUL && RING == 0), "dynamic dealing is the plain kernels'");
     static_assert(!(LEANV & kLeanMoments) || (MODE == kFastMoments && NA >= 1), "the lean layout is moments mode's");
     static_assert(!(LEANV & kLeanProved) || MODE == kFastMoments || MODE == kFastHist, "the proved bodies are the bucket modes'");
     extern __shared__ int64_t lds[];
@@ -484,7 +689,10 @@ __global__ __launch_bounds__(kWgThreads, SYBL_PACKED_WAVES_PER_EU) void k_scan_p
     const FastLds L = fast_begin<MODE>(P, lds, kMax32 && !P.ext_general, lean_layout);
 
     uint32_t matched = 0, overflow = 0;
-    const int s0 = P.wg_seg_begin[blockIdx.x], s1 = P.wg_seg_begin[blockIdx.x + 1];
+    const uint64_t clock_in = P.wg_clock ? wall_clock64() : 0;  // (SYBL_WG_CLOCKS=1: when this workgroup's loop began and ended)
+    if constexpr (DYN) packed_scan_dyn<NF, NG, NA, MODE, TIME, G1, LEANV>(P, lds, L, kMax32 && !P.ext_general, matched, overflow);
+    // (DYN: no segments -- the static loops below compile to nothing)
+    const int s0 = DYN ? 0 : P.wg_seg_begin[blockIdx.x], s1 = DYN ? 0 : P.wg_seg_begin[blockIdx.x + 1];
     for (int si = s0; si < s1; si++) {
         const Segment seg = P.segs[si];
         for (int64_t c0 = 0; c0 < seg.n; c0 += kPackedChunkRows) {
@@ -699,8 +907,13 @@ __global__ __launch_bounds__(kWgThreads, SYBL_PACKED_WAVES_PER_EU) void k_scan_p
             }
         }
     }
+    const uint64_t clock_out = P.wg_clock ? wall_clock64() : 0;
     // (!NUL: no row body counted overflow -- fast_finish derives it)
     fast_finish(P, lds, L, matched, overflow, kMax32 && !P.ext_general, lean_layout ? (uint32_t)NA : 0u, !NUL);
+    if (P.wg_clock && tid == 0) {
+        P.wg_clock[2 * blockIdx.x] = clock_in;
+        P.wg_clock[2 * blockIdx.x + 1] = clock_out;
+    }
 }
 
 // k_emit over compact storage (strategy 5, see k_emit in scan_fast.h): the same records, staged and
@@ -1139,6 +1352,31 @@ static hipError_t packed_launch_k1(const FastPlan &P, int n_wg, size_t lds_bytes
         hipLaunchKernelGGL(kern, dim3(n_wg), dim3(kWgThreads), lds_bytes, st, P);
         return hipGetLastError();
     };
+    // FastPlan::dyn: the kernels with the dynamic loops (the planner takes it for plans without NUL only, and not beside
+    // SYBL_PACKED_RING); a missing kernel is an error
+    if (P.dyn) {
+        if constexpr (!NUL) {
+            if (!P.pieces || !P.piece_queue || P.n_pieces < 1 || P.piece_cap < 1) return hipErrorInvalidValue;
+            if constexpr (NA >= 1 && MODE == kFastMoments) {
+                switch (P.lean) {
+                case 0: return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, NUL, 0, 0, true>);
+                case kLeanMoments: return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, NUL, 0, kLeanMoments, true>);
+                case kLeanProved: return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, NUL, 0, kLeanProved, true>);
+                case kLeanMoments | kLeanProved: return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, NUL, 0, kLeanMoments | kLeanProved, true>);
+                default: return hipErrorInvalidValue;
+                }
+            } else if constexpr (NA >= 1 && MODE == kFastHist) {
+                if (P.lean == kLeanProved) return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, NUL, 0, kLeanProved, true>);
+                if (P.lean) return hipErrorInvalidValue;
+                return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, NUL, 0, 0, true>);
+            } else {
+                if (P.lean) return hipErrorInvalidValue;
+                return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, NUL, 0, 0, true>);
+            }
+        } else {
+            return hipErrorInvalidValue;
+        }
+    }
     // FastPlan::lean: the kernel must be the one the planner sized the table for.  (The lean kernels have no ring variants:
     // SYBL_PACKED_RING acts on a plan without lean -- set SYBL_NO_LEAN=1 beside it.)
     if (P.lean) {
