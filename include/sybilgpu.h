@@ -694,6 +694,75 @@ typedef struct {
 } sybl_select_stats;
 int sybl_table_select_stats(const sybl_table *t, sybl_select_stats *out);
 
+/* ------------------------------------------------------------------ concat
+ * Resident tables joined end to end as a NEW resident table: the call that takes more than one table.  Its uses: folding a
+ * small table of arrivals into a big digested one (digest the arrivals, concat, free both: a streaming copy, not a sort of
+ * everything); one table out of tables kept per day or per shard; putting two selects back together.  The reference has no
+ * such call: the semantics are this library's.  Dictionaries are table-global and compact storage is per table, so the
+ * rows are RE-ENCODED where the stored forms differ; that runs on the GPU (csrc/concat.hip).  Restated deterministically:
+ *   source rows: for each source in the order given, the logical rows of its live blocks in resident order.  Blocks without
+ *     rows (left behind by sybl_table_refresh) and the padding of a block to 32 rows contribute nothing.  A table may
+ *     appear more than once; one table alone gives a copy of it.
+ *   blocks: block boundaries are KEPT -- the output's blocks are the sources' live non-empty blocks in that order, output
+ *     block k starting at the next multiple of 32 physical rows.  Nothing is re-cut (sybl_table_select without filters
+ *     does that) and nothing is sorted (sybl_table_digest does that).  Zero rows in total: the columns and no blocks, and
+ *     no kernel runs.
+ *   columns: NULL or 0 = the union of the sources' columns in first-seen order (source 0's columns in its order, then each
+ *     later source's new ones); otherwise the named columns in the order named, each once (a name given again is
+ *     ignored).  A name that no source holds: SYBL_E_INVAL.  The same name with different types in two sources:
+ *     SYBL_E_INVAL, the message names the column and both tables.  A source that lacks an output column contributes
+ *     unpopulated rows for its blocks.
+ *   dictionaries (str / set): the output dictionary is the first holder's (source 0's, when it holds the column) id for id,
+ *     then, for each later source in order, that source's strings in its id order where the output does not hold them yet.
+ *     Every source's WHOLE dictionary takes part, used by a row or not.  So the first holder's ids are unchanged and the
+ *     others go through one id -> id table per (source, column); a later source whose table is the identity needs none.
+ *   storage: the output is in compact mode iff EVERY source is.  In compact mode each int / str column is stored, as
+ *     sybl_table_compact stores it, at the narrowest of 1 / 2 / 4 / 8 bytes that holds hi - lo, as offsets from base lo
+ *     (the canonical width -- 8 for ints, 4 for str ids -- has base 0).  For an int column [lo, hi] is the union of the
+ *     tracked extrema (sybl_table_column_info: exact_min, exact_max) of the sources that hold it; for a str column the
+ *     union, over the sources, of the tracked id extrema [a, b] -- for a source with an id table T, of min and max of
+ *     T[a..b].  A column with no populated row anywhere: width 1, base 0.  Otherwise canonical: int64 values, int32 ids,
+ *     base 0.  sybl_table_column_storage reports it.
+ *   validity: an output column has a bitmap iff some source column has one, or some source with rows lacks the column.
+ *     Padding bits are zero.
+ *   inherited: the type; IntInfo -- given iff every source holding the column was given one, then the minimum of the minima
+ *     and the maximum of the maxima, otherwise the exact extrema are in force as for info_min > info_max; has_missing --
+ *     the OR over the sources, or true when a source with rows lacks the column.  NOT inherited: declared bounds
+ *     (sybl_table_set_bounds speaks of another table's ranks), group dictionaries, rank columns, carried weights: the next
+ *     prepare builds them.
+ *   statistics: per-block min / max / populated counts and the table-wide extrema are exact or the sources' own (bounds of
+ *     a superset are bounds); those of a str column whose ids went through an id table are recomputed.
+ * The output has source 0's ctx and name, is attached to no directory, owns everything it shows and outlives every source;
+ * free it with sybl_table_free.  The sources are untouched and their versions do not move: a query prepared on a source
+ * before the call still scans afterwards.  Sources of different contexts, n_tables < 1, a NULL entry, NULL d or out:
+ * SYBL_E_INVAL, sybl_last_error begins "sybl_table_concat: ".  When HBM runs out: SYBL_E_NOMEM, everything freed, *out NULL.
+ * Rank-local, never collective; runs on the ctx stream, is complete on return and thread-safe per ctx like select.  There
+ * is no 2^31 or 2^32 row limit: nothing is sorted and no row numbers travel.  A table with set columns pays a host pass
+ * per set column (their CSR is concatenated on the host). */
+typedef struct {
+    int32_t n_tables;
+    sybl_table *const *tables;     /* >= 1, same ctx; a table may appear more than once */
+    int32_t n_columns;
+    const char *const *columns;    /* columns of the output; NULL / 0 = the union of the sources' columns */
+} sybl_concat_desc;
+
+int sybl_table_concat(const sybl_concat_desc *d, sybl_table **out);
+
+/* What the sybl_table_concat that made this table did (zeros for any other table).  A piece is one (source, int / str
+ * output column) pair of a source with rows that holds the column. */
+typedef struct {
+    int64_t rows, blocks;    /* of the output */
+    int32_t tables, columns; /* sources given, output columns */
+    int32_t copies;          /* pieces in the output's stored form: device-to-device copies */
+    int32_t transcodes;      /* pieces re-encoded at another width / base (k_cc_transcode) */
+    int32_t lut_transcodes;  /* ... and through an id table */
+    int32_t runs;            /* runs of consecutive live blocks, over all sources */
+    double copy_ms;          /* hipEvent time of all device copies, transcodes and validity words */
+    double stats_ms;         /* ... of the recomputed block statistics */
+    int64_t copy_bytes;      /* bytes copy_ms moved (read + written), computed from the shapes */
+} sybl_concat_stats;
+int sybl_table_concat_stats(const sybl_table *t, sybl_concat_stats *out);
+
 /* Test hook (no GPU needed): the library's regular-expression engine for re / nre str filters -- Go regexp
  * (RE2) syntax, unanchored search like regexp.MatchString (filter.go:213-236).  1 = match, 0 = no match,
  * -1 = the pattern does not compile (sybl_last_error says why). */

@@ -141,6 +141,20 @@ class SelectStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ConcatDesc(C.Structure):
+    _fields_ = [("n_tables", C.c_int32), ("tables", C.POINTER(C.c_void_p)), ("n_columns", C.c_int32),
+                ("columns", C.POINTER(C.c_char_p))]
+
+
+class ConcatStats(C.Structure):
+    _fields_ = [("rows", C.c_int64), ("blocks", C.c_int64), ("tables", C.c_int32), ("columns", C.c_int32),
+                ("copies", C.c_int32), ("transcodes", C.c_int32), ("lut_transcodes", C.c_int32), ("runs", C.c_int32),
+                ("copy_ms", C.c_double), ("stats_ms", C.c_double), ("copy_bytes", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol include/sybilgpu.h declares: (restype, argtypes)
 P = C.c_void_p
 SIGNATURES = {
@@ -223,6 +237,8 @@ SIGNATURES = {
     "sybl_table_digest_stats": (C.c_int, [P, C.POINTER(DigestStats)]),
     "sybl_table_select": (C.c_int, [P, C.POINTER(SelectDesc), C.POINTER(P)]),
     "sybl_table_select_stats": (C.c_int, [P, C.POINTER(SelectStats)]),
+    "sybl_table_concat": (C.c_int, [C.POINTER(ConcatDesc), C.POINTER(P)]),
+    "sybl_table_concat_stats": (C.c_int, [P, C.POINTER(ConcatStats)]),
 }
 
 _lib = None

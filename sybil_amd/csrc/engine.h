@@ -206,6 +206,7 @@ struct Table {
     sybl_load_stats load_stats{};  // of the sybl_table_open / sybl_table_refresh that last loaded blocks
     sybl_digest_stats digest_stats{};  // of the sybl_table_digest that made this table (digest.hip)
     sybl_select_stats select_stats{};  // of the sybl_table_select that made this table (select.hip)
+    sybl_concat_stats concat_stats{};  // of the sybl_table_concat that made this table (concat.hip)
     std::string src_dir;           // <dir>/<table> the table was opened from ("" = built through the ABI)
     int src_rank = 0, src_nranks = 1;
     std::vector<LoadedBlock> loaded;
@@ -553,6 +554,7 @@ void json_escape(const std::string &s, std::string &o);  // render.cpp: a string
 int samples_run(Table *t, const sybl_samples_desc *d, sybl_samples **out);  // samples.hip
 int digest_run(Table *t, const char *time_col, int32_t block_rows, sybl_table **out);  // digest.hip
 int select_run(Table *t, const sybl_select_desc *d, sybl_table **out);  // select.hip
+int concat_run(const sybl_concat_desc *d, sybl_table **out);  // concat.hip
 int query_rescan_without_part_hist(Query *q);
 
 constexpr int kMaxScatterRanks = 64;  // the SUM section is padded so that a reduce-scatter over up to this many ranks fits in place

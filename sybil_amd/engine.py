@@ -96,6 +96,20 @@ class Context:
                                               C.byref(h)))
         return Table(self, h, table)
 
+    def concat(self, tables, columns=None):
+        """The rows of `tables` (Tables of this context, one may appear more than once) joined end to end, block boundaries
+        kept, as a NEW resident table holding `columns` (None = the union of the tables' columns) in the order named
+        (sybl_table_concat).  The tables are untouched; free them and the result."""
+        d = N.ConcatDesc()
+        harr = (C.c_void_p * max(len(tables), 1))(*[t._h.value for t in tables])
+        d.n_tables, d.tables = len(tables), C.cast(harr, C.POINTER(C.c_void_p))
+        names = [_b(c) for c in columns] if columns is not None else []
+        carr = (C.c_char_p * max(len(names), 1))(*names)
+        d.n_columns, d.columns = len(names), (C.cast(carr, C.POINTER(C.c_char_p)) if names else None)
+        h = C.c_void_p()
+        N.check(N.lib().sybl_table_concat(C.byref(d), C.byref(h)))
+        return Table(self, h, tables[0].name)
+
 
 class Table:
     def __init__(self, ctx, handle, name):
@@ -321,6 +335,12 @@ class Table:
         """Device time and bytes of the phases of the select() that made this table (sybl_table_select_stats)."""
         st = N.SelectStats()
         N.check(N.lib().sybl_table_select_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
+    def concat_stats(self):
+        """Pieces, device time and bytes of the Context.concat() that made this table (sybl_table_concat_stats)."""
+        st = N.ConcatStats()
+        N.check(N.lib().sybl_table_concat_stats(self._h, C.byref(st)))
         return st.as_dict()
 
     def query(self, filters=(), groups=(), aggs=(), op="avg", hist_bucket=0, want_percentiles=True, time_col=None,
