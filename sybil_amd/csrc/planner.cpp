@@ -1831,6 +1831,12 @@ struct Planner {
         select_fast_path(t, q, slot_col);
         select_hash_fast(t, q, slot_col);
         prefilter_commit();
+        // SYBL_PLAN_TRACE=1 (diagnostic): both table levels of a hashed query (lds_bytes alone does not tell the staging slots
+        // from the words of one) and the row body in front of them; late: k_scan_hash_packed's LATE instantiation (hashpacked.hip)
+        if (q->hash_mode && env("SYBL_PLAN_TRACE"))
+            fprintf(stderr, "hash tables: slots=%lld staging=%d words_per_slot=%d kernel=%s late=%d\n", (long long)n_cells, (int)P.lds_cells, 1 + F + M,
+                    !q->hash_fast ? "generic" : q->hash_packed ? "packed" : "fast",
+                    q->hash_fast && q->hash_packed && q->fast_nf > 0 && q->fplan.late && !q->fplan.nul ? 1 : 0);
         if ((rc = select_part_hist(t, q, slot_col, rows_scanned))) return rc;
         plan_dynamic();  // (plan_count_packing and plan_lean, for the dealing it takes)
         if ((rc = plan_pushdown())) return rc;
