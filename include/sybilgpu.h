@@ -763,6 +763,77 @@ typedef struct {
 } sybl_concat_stats;
 int sybl_table_concat_stats(const sybl_table *t, sybl_concat_stats *out);
 
+/* ------------------------------------------------------------------ lookup
+ * Columns of a second resident table attached by key, as a NEW resident table: what adds a column that comes from somewhere
+ * else.  A table is an event log of ids (user, host, build); what the ids mean lives in a small second table `dim` (host to
+ * datacenter, build to release date).  For every row of t the call finds the row of dim whose key equals the row's key and
+ * attaches chosen columns of that dim row: a LEFT JOIN with FIRST MATCH, in broadcast form -- every rank holds all of dim.
+ * The reference has no join: the semantics are this library's.  Key table, probe and gather run on the GPU (csrc/lookup.hip);
+ * everything behind the call is a plain scan of a resident table.  Restated deterministically:
+ *   rows and blocks: exactly what sybl_table_concat of t alone gives -- t's live non-empty blocks in resident order, block
+ *     boundaries kept, each block starting on a multiple of 32 physical rows; dead blocks and padding contribute nothing.
+ *     The columns of t come out as that concat gives them: values, dictionaries, storage, validity, statistics, and the list
+ *     of what is not inherited.  t without rows: all the columns (attached ones included), no blocks, and no kernel runs.
+ *   keys: `key` names the key column of t, `dim_key` that of dim (NULL or "" = the name given in key).  Both are INT columns
+ *     or both are STR columns; a SET key, two key types, or a name the table does not hold: SYBL_E_INVAL, the message names
+ *     the column.  INT keys compare as decoded int64 values -- the stored width and base may differ between the tables.  STR
+ *     keys compare as strings, not ids: the two dictionaries are unrelated.  A row of t whose key is unpopulated matches
+ *     nothing; rows of dim whose key is unpopulated take no part.
+ *   which dim row: among the live dim rows with a populated key equal to the row's key, the FIRST in resident order.  The
+ *     later ones are counted (sybl_lookup_stats.dim_duplicates).  dim without rows: nothing matches.
+ *   attached columns: `columns` names the dim columns to attach, in the order named, each once (a name given again is
+ *     ignored); NULL or 0 = every dim column except dim_key, in dim's order.  dim_key itself may be attached when it is
+ *     named.  A name dim lacks: SYBL_E_INVAL.  An attached column is named prefix + name (prefix NULL = ""); a name the
+ *     output already holds -- a column of t, or an earlier attached one --: SYBL_E_INVAL naming it.  For output row r with
+ *     match m the value is dim's value at row m; it is populated iff there is a match and dim's value at m is populated;
+ *     where it is unpopulated the stored bytes are 0.  An attached column inherits the dim column's type, IntInfo and
+ *     dictionary id for id.  Declared bounds (sybl_table_set_bounds) are NOT inherited, as in concat.  has_missing is dim's
+ *     OR "some row of t found no match".  It has a validity bitmap iff the dim column has one or some row found no match;
+ *     padding bits are zero.
+ *   storage: the output is in compact mode iff t is.  In compact mode each attached int / str column is stored at the
+ *     narrowest of 1 / 2 / 4 / 8 bytes that holds the dim column's tracked extrema (for a str column: of its ids), as
+ *     offsets from the minimum -- concat's rule; a column with no populated row: width 1, base 0.  Otherwise canonical: int64
+ *     values, int32 ids, base 0.  The stored form of a dim column and of its output column can differ: the gather re-encodes.
+ *   set columns of dim may be attached; as in digest and concat their CSR is built on the host, from the match list.
+ *   statistics: per-block min / max / populated counts of the attached columns are exact; table-wide extrema may be dim's
+ *     (bounds of a superset are bounds).
+ * dim may hold at most 2^32 - 2 physical rows (the all-ones row number means "no match"); beyond: SYBL_E_INVAL.  An INT key
+ * whose values are too spread for a direct table goes through a hash table of at most kHashMaxSlots = 2^27 slots; a dim that
+ * needs more: SYBL_E_INVAL, the message says so.  t has no row limit.  When HBM runs out: SYBL_E_NOMEM, everything freed,
+ * *out NULL.  NULL t, d, out or d->dim, a dim of another context, a negative n_columns: SYBL_E_INVAL; sybl_last_error begins
+ * "sybl_table_lookup: ".
+ * Both sources are untouched and their versions do not move: a query prepared on either before the call still scans
+ * afterwards.  dim may be t itself.  The output has t's ctx and name, is attached to no directory, owns everything it shows
+ * and outlives both sources; free it with sybl_table_free.  Rank-local, never collective; runs on the ctx stream, is complete
+ * on return and thread-safe per ctx like select.
+ * Out of scope: inner joins (follow with sybl_table_select on an attached column); many-to-many expansion (one dim row per
+ * row of t, the first); composite keys; a CLI flag; any distribution of dim across ranks. */
+typedef struct {
+    sybl_table *dim;              /* same ctx as t; may be t itself */
+    const char *key;              /* key column of t */
+    const char *dim_key;          /* key column of dim; NULL or "" = the name given in key */
+    int32_t n_columns;
+    const char *const *columns;   /* dim columns to attach; NULL / 0 = every dim column except dim_key, in dim's order */
+    const char *prefix;           /* put before each attached column's name; NULL = "" */
+} sybl_lookup_desc;
+
+int sybl_table_lookup(sybl_table *t, const sybl_lookup_desc *d, sybl_table **out);
+
+/* What the sybl_table_lookup that made this table did (zeros for any other table): the device time of its phases and the
+ * bytes each moves, computed from the shapes. */
+typedef struct {
+    int64_t rows, blocks;                         /* of the output */
+    int64_t dim_rows, dim_keys, dim_duplicates;   /* live dim rows; distinct populated keys; populated dim rows - dim_keys */
+    int64_t matched;                              /* rows of t that found a dim row */
+    int64_t slots;                                /* hash path: slots of the table, else 0 */
+    int32_t path;          /* 1 = direct over the key's range, 2 = hash, 3 = str ids; 0 = no key table was built (t or dim
+                              without rows, no populated dim key) */
+    int32_t columns;       /* attached */
+    double build_ms, probe_ms, gather_ms;             /* hipEvent time: key table; probe; gather, validity, block statistics */
+    int64_t build_bytes, probe_bytes, gather_bytes;
+} sybl_lookup_stats;
+int sybl_table_lookup_stats(const sybl_table *t, sybl_lookup_stats *out);
+
 /* Test hook (no GPU needed): the library's regular-expression engine for re / nre str filters -- Go regexp
  * (RE2) syntax, unanchored search like regexp.MatchString (filter.go:213-236).  1 = match, 0 = no match,
  * -1 = the pattern does not compile (sybl_last_error says why). */

@@ -155,6 +155,21 @@ class ConcatStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class LookupDesc(C.Structure):
+    _fields_ = [("dim", C.c_void_p), ("key", C.c_char_p), ("dim_key", C.c_char_p), ("n_columns", C.c_int32),
+                ("columns", C.POINTER(C.c_char_p)), ("prefix", C.c_char_p)]
+
+
+class LookupStats(C.Structure):
+    _fields_ = [("rows", C.c_int64), ("blocks", C.c_int64), ("dim_rows", C.c_int64), ("dim_keys", C.c_int64),
+                ("dim_duplicates", C.c_int64), ("matched", C.c_int64), ("slots", C.c_int64), ("path", C.c_int32),
+                ("columns", C.c_int32), ("build_ms", C.c_double), ("probe_ms", C.c_double), ("gather_ms", C.c_double),
+                ("build_bytes", C.c_int64), ("probe_bytes", C.c_int64), ("gather_bytes", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol include/sybilgpu.h declares: (restype, argtypes)
 P = C.c_void_p
 SIGNATURES = {
@@ -239,6 +254,8 @@ SIGNATURES = {
     "sybl_table_select_stats": (C.c_int, [P, C.POINTER(SelectStats)]),
     "sybl_table_concat": (C.c_int, [C.POINTER(ConcatDesc), C.POINTER(P)]),
     "sybl_table_concat_stats": (C.c_int, [P, C.POINTER(ConcatStats)]),
+    "sybl_table_lookup": (C.c_int, [P, C.POINTER(LookupDesc), C.POINTER(P)]),
+    "sybl_table_lookup_stats": (C.c_int, [P, C.POINTER(LookupStats)]),
 }
 
 _lib = None

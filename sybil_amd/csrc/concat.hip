@@ -136,6 +136,22 @@ __global__ __launch_bounds__(kCcThreads) void k_cc_valid(const uint32_t *__restr
     out[(B.dst >> 5) + w] = bits;
 }
 
+// (gather.h; shared with lookup.hip) table.cpp's fit_storage: the narrowest (width, base) that holds [lo, hi]; canonical storage when nothing narrower does
+void concat_fit(const Column *c, bool any, int64_t lo, int64_t hi, int *width, int64_t *base) {
+    *width = c->canon();
+    *base = 0;
+    if (!any) {
+        *width = 1;
+        return;
+    }
+    const unsigned __int128 range = (unsigned __int128)((__int128)hi - (__int128)lo);
+    const int f = range < 256 ? 1 : range < 65536 ? 2 : range < ((unsigned __int128)1 << 32) ? 4 : 8;
+    if (f < *width) {
+        *width = f;
+        *base = lo;
+    }
+}
+
 namespace {
 
 inline unsigned grid_for(int64_t n, int threads) { return (unsigned)std::max<int64_t>(1, (n + threads - 1) / threads); }
@@ -182,22 +198,6 @@ bool launch_transcode(int ws, int wd, const CcPiece &p, hipStream_t st) {
     }
 #undef CC_PAIR
 #undef CC_PAIR_PLAIN
-}
-
-// table.cpp's fit_storage: the narrowest (width, base) that holds [lo, hi]; canonical storage when nothing narrower does
-void fit(const Column *c, bool any, int64_t lo, int64_t hi, int *width, int64_t *base) {
-    *width = c->canon();
-    *base = 0;
-    if (!any) {
-        *width = 1;
-        return;
-    }
-    const unsigned __int128 range = (unsigned __int128)((__int128)hi - (__int128)lo);
-    const int f = range < 256 ? 1 : range < 65536 ? 2 : range < ((unsigned __int128)1 << 32) ? 4 : 8;
-    if (f < *width) {
-        *width = f;
-        *base = lo;
-    }
 }
 
 struct Source {
@@ -353,7 +353,7 @@ int run(const sybl_concat_desc *d, Table *o, sybl_concat_stats *S) {
             hi = std::max(hi, b);
             pop += c->n_pop;
         }
-        if (compact) fit(n, any, lo, hi, &n->elem, &n->vbase);
+        if (compact) concat_fit(n, any, lo, hi, &n->elem, &n->vbase);
         n->exact_min = lo;
         n->exact_max = hi;
         n->n_pop = pop;

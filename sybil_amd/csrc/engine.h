@@ -207,6 +207,7 @@ struct Table {
     sybl_digest_stats digest_stats{};  // of the sybl_table_digest that made this table (digest.hip)
     sybl_select_stats select_stats{};  // of the sybl_table_select that made this table (select.hip)
     sybl_concat_stats concat_stats{};  // of the sybl_table_concat that made this table (concat.hip)
+    sybl_lookup_stats lookup_stats{};  // of the sybl_table_lookup that made this table (lookup.hip)
     std::string src_dir;           // <dir>/<table> the table was opened from ("" = built through the ABI)
     int src_rank = 0, src_nranks = 1;
     std::vector<LoadedBlock> loaded;
@@ -555,6 +556,7 @@ int samples_run(Table *t, const sybl_samples_desc *d, sybl_samples **out);  // s
 int digest_run(Table *t, const char *time_col, int32_t block_rows, sybl_table **out);  // digest.hip
 int select_run(Table *t, const sybl_select_desc *d, sybl_table **out);  // select.hip
 int concat_run(const sybl_concat_desc *d, sybl_table **out);  // concat.hip
+int lookup_run(Table *t, const sybl_lookup_desc *d, sybl_table **out);  // lookup.hip
 int query_rescan_without_part_hist(Query *q);
 
 constexpr int kMaxScatterRanks = 64;  // the SUM section is padded so that a reduce-scatter over up to this many ranks fits in place

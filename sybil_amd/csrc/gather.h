@@ -57,4 +57,9 @@ void gather_make_columns(const Table *t, const std::vector<Column *> &src, Table
 int gather_rows(Table *t, const std::vector<Column *> &src, const uint32_t *rows, int64_t N, int64_t block_rows, Table *o, GatherPool &pool,
                 const char *who, hipEvent_t *gathered, int64_t *bytes, int64_t *blocks);
 
+// concat.hip: the (width, base) of a compact column whose tracked extrema are [lo, hi] (any = false: no populated row -- width 1,
+// base 0): the narrowest of 1 / 2 / 4 / 8 bytes that holds hi - lo, offsets from lo; the canonical width has base 0.  Shared with
+// lookup.hip.
+void concat_fit(const Column *c, bool any, int64_t lo, int64_t hi, int *width, int64_t *base);
+
 }  // namespace sybl

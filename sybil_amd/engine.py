@@ -343,6 +343,29 @@ class Table:
         N.check(N.lib().sybl_table_concat_stats(self._h, C.byref(st)))
         return st.as_dict()
 
+    def lookup(self, dim, key, dim_key=None, columns=None, prefix=""):
+        """For every row of this table the FIRST row of `dim` (a Table of the same context, possibly this one) whose `dim_key`
+        (None = `key`) equals the row's `key`; `columns` of that row (None = every dim column but the key) attached as columns
+        named prefix + name of a NEW resident table with this table's rows and blocks (sybl_table_lookup): a left join, rows
+        without a match get unpopulated values.  Both tables are untouched; free them and the result."""
+        d = N.LookupDesc()
+        d.dim = dim._h.value
+        d.key = _b(key)
+        d.dim_key = _b(dim_key) if dim_key is not None else None
+        names = [_b(c) for c in columns] if columns is not None else []
+        carr = (C.c_char_p * max(len(names), 1))(*names)
+        d.n_columns, d.columns = len(names), (C.cast(carr, C.POINTER(C.c_char_p)) if names else None)
+        d.prefix = _b(prefix) if prefix is not None else None
+        h = C.c_void_p()
+        N.check(N.lib().sybl_table_lookup(self._h, C.byref(d), C.byref(h)))
+        return Table(self.ctx, h, self.name)
+
+    def lookup_stats(self):
+        """Path, counts, device time and bytes of the phases of the lookup() that made this table (sybl_table_lookup_stats)."""
+        st = N.LookupStats()
+        N.check(N.lib().sybl_table_lookup_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
     def query(self, filters=(), groups=(), aggs=(), op="avg", hist_bucket=0, want_percentiles=True, time_col=None,
               time_bucket=0, weight_col=None, order_by="$COUNT", order_asc=False, limit=0, block_skip=False, loghist=False, str_replace=(),
               distincts=(), printed_only=False):
