@@ -63,6 +63,7 @@ hipError_t launch_gob_values(const GobValuesBatch &B, hipStream_t st);  // gobgp
 hipError_t launch_hist_summary(const HistSummaryPlan &S, int64_t *total, hipStream_t st);
 hipError_t launch_rank_column(const void *col, int width, int64_t vbase, const uint32_t *valid, const int64_t *dkeys, const int32_t *dranks, uint32_t dmask,
                               int64_t n, void *out, int ow, uint32_t miss, hipStream_t st);
+hipError_t launch_narrow3(const void *src, void *dst, int64_t row0, int64_t rows, hipStream_t st);
 hipError_t launch_weight_carry(const void *col, int width, int64_t vbase, const uint32_t *valid, const Segment *d_blocks, int n_blocks, int64_t *out, hipStream_t st);
 hipError_t launch_hist_total(const int64_t *H, int64_t hist_stride, int64_t cell0, int64_t cell1, int64_t *total, hipStream_t st);
 hipError_t launch_hist_gather(const int64_t *H, int64_t hist_stride, const int64_t *d_cells, int64_t n, int64_t cell0, int64_t cell1,
@@ -163,6 +164,16 @@ struct Column {
     // (round 6: every prepare used to build its own -- a pass over the column and 8 B/row of HBM per weighted query).
     std::shared_ptr<Column> carried_weight;
     int64_t carried_version = -1;
+    // A 4-byte int column whose largest stored offset (exact_max - vbase) is below 2^24: the same offsets at THREE bytes a row
+    // (narrow3.h; table.cpp: column_build_narrow), which k_scan_packed reads in the column's place as an aggregation input --
+    // a quarter fewer bytes per scan, paid once per table version.  elem 3, this column's vbase, so every stored offset and
+    // every planner proof about offsets is unchanged; validity stays this column's d_valid (the twin has none of its own).
+    // Not a storage width: sybl_table_column_storage and every table-to-table feature see 1 / 2 / 4 / 8 as before.
+    // narrow_rows: the physical rows it covers; valid for (narrow_version, narrow_blocks) = (Table::version, blocks) it was
+    // last checked against.  A prepared query's pointer follows rank_col's rules: same version, same buffer; a moved version
+    // fails sybl_query_scan before any kernel reads it.
+    std::unique_ptr<Column> narrow;
+    int64_t narrow_rows = 0, narrow_version = -1, narrow_blocks = 0;
     // table-global dictionary (str / set)
     std::vector<std::string> dict;
     std::unordered_map<std::string, int32_t> dict_ix;
@@ -226,6 +237,10 @@ int32_t dict_intern(Column *c, const std::string &s);
 int column_upload_set(Table *t, Column *c);
 int column_build_gdict(Table *t, Column *c);           // distinct values of the resident rows
 int column_build_rank(Table *t, Column *c);            // Column::rank_col for the current dictionary and table version
+// Column::narrow for the current table version, or nullptr: the column is not eligible, the feature is off, or HBM is short
+// (never an error of the query: the plan keeps the 4-byte column)
+Column *column_build_narrow(Table *t, Column *c);
+void column_drop_narrow(Column *c);
 int column_install_gdict(Table *t, Column *c);         // sorted gdict -> device value->rank map
 int column_repack(Table *t, Column *c, int width, int64_t vbase);  // change the stored width in place
 

@@ -211,6 +211,7 @@ static hipError_t hash_fast_mode(const FastPlan &P, uint64_t *keys, int nf, int 
 
 hipError_t launch_scan_hash_fast(const FastPlan &P, uint64_t *keys, int nf, int ng, int na, int mode, bool time, int L, int F, int M, int n_wg,
                                  size_t lds_bytes, hipStream_t st) {
+    if (fast_plan_has_narrow(P, true)) return hipErrorInvalidValue;  // (a narrow twin: k_scan_packed's aggregation columns only)
     switch (na) {
     case 0: return hash_fast_mode<0>(P, keys, nf, ng, mode, time, L, F, M, n_wg, lds_bytes, st);
     case 1: return hash_fast_mode<1>(P, keys, nf, ng, mode, time, L, F, M, n_wg, lds_bytes, st);

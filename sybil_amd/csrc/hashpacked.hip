@@ -537,12 +537,14 @@ __global__ __launch_bounds__(kWgThreads) void k_prefilter_packed(const FastPlan 
 }
 
 hipError_t launch_prefilter_packed(const FastPlan &P, int nf, uint32_t *bits, bool and_into, int n_wg, hipStream_t st) {
+    if (fast_plan_has_narrow(P, true)) return hipErrorInvalidValue;  // (a narrow twin: k_scan_packed's aggregation columns only)
     if (and_into) hipLaunchKernelGGL(k_prefilter_packed<true>, dim3(n_wg), dim3(kWgThreads), 0, st, P, nf, bits);
     else hipLaunchKernelGGL(k_prefilter_packed<false>, dim3(n_wg), dim3(kWgThreads), 0, st, P, nf, bits);
     return hipGetLastError();
 }
 
 hipError_t launch_scan_packed_n(const FastPlan &P, int nf, int ng, int na, int mode, bool time, int n_wg, size_t lds_bytes, hipStream_t st) {
+    if (fast_plan_has_narrow(P, true)) return hipErrorInvalidValue;  // (a narrow twin: k_scan_packed's aggregation columns only)
     switch (na) {
     case 0: return packed_n_mode<0>(P, nf, ng, mode, time ? 1 : 0, n_wg, lds_bytes, st);
     case 1: return packed_n_mode<1>(P, nf, ng, mode, time ? 1 : 0, n_wg, lds_bytes, st);
@@ -555,6 +557,7 @@ hipError_t launch_scan_packed_n(const FastPlan &P, int nf, int ng, int na, int m
 
 hipError_t launch_scan_hash_packed(const FastPlan &P, uint64_t *keys, int nf, int ng, int na, int mode, bool time, int L, int F, int M, int n_wg,
                                    size_t lds_bytes, hipStream_t st) {
+    if (fast_plan_has_narrow(P, true)) return hipErrorInvalidValue;  // (a narrow twin: k_scan_packed's aggregation columns only)
     switch (na) {
     case 0: return hash_packed_mode<0>(P, keys, nf, ng, mode, time ? 1 : 0, L, F, M, n_wg, lds_bytes, st);
     case 1: return hash_packed_mode<1>(P, keys, nf, ng, mode, time ? 1 : 0, L, F, M, n_wg, lds_bytes, st);

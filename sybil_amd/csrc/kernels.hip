@@ -27,6 +27,7 @@
 
 #include "plan.h"
 #include "gob_bins.h"
+#include "narrow3.h"
 #include "scan_fast.h"
 #include "scan_generic.h"
 
@@ -347,6 +348,33 @@ hipError_t launch_rank_column(const void *col, int width, int64_t vbase, const u
     const int64_t blocks = (n + 255) / 256;
     hipLaunchKernelGGL(k_rank_column, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, st, col, width, vbase, valid, dkeys, dranks, dmask, n, out,
                        ow, miss);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- a 4-byte column's narrow twin (narrow3.h)
+// The stored offsets of quads [q0, q0 + n) -- four consecutive rows each -- at three bytes a row: a thread reads one quad with
+// a 16-byte load and writes its twelve bytes (three dwords at a 12-byte stride: dword-aligned, not more).  The offsets are
+// copied as they are; rows without a value carry don't-care bits in both columns.
+__global__ __launch_bounds__(256) void k_narrow3(const uint32_t *__restrict__ src, uint32_t *__restrict__ dst, int64_t q0, int64_t n) {
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (int64_t)gridDim.x * blockDim.x) {
+        typedef uint32_t quad_t __attribute__((ext_vector_type(4)));
+        const quad_t v = __builtin_nontemporal_load((const quad_t *)src + (q0 + q));
+        const uint32_t u[4] = {v.x, v.y, v.z, v.w};
+        uint32_t d[3];
+        pack3(u, d);
+        uint32_t *o = dst + 3 * (q0 + q);
+        __builtin_nontemporal_store(d[0], o);
+        __builtin_nontemporal_store(d[1], o + 1);
+        __builtin_nontemporal_store(d[2], o + 2);
+    }
+}
+// rows [row0, row0 + rows) of the 4-byte column `src` into the twin `dst`; row0 a multiple of 4, and both arrays hold the
+// whole last quad (every column is reserved a tile beyond its rows: table_reserve)
+hipError_t launch_narrow3(const void *src, void *dst, int64_t row0, int64_t rows, hipStream_t st) {
+    if (rows <= 0) return hipSuccess;
+    if (row0 & 3) return hipErrorInvalidValue;
+    const int64_t quads = (rows + 3) / 4, blocks = (quads + 255) / 256;
+    hipLaunchKernelGGL(k_narrow3, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, st, (const uint32_t *)src, (uint32_t *)dst, row0 / 4, quads);
     return hipGetLastError();
 }
 

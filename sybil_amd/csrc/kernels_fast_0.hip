@@ -16,6 +16,7 @@ hipError_t launch_scan_fast_nf0(const FastPlan &P, int ng, int na, int mode, boo
 
 hipError_t launch_scan_fast(const FastPlan &P, int nf, int ng, int na, int mode, bool time, bool gen, int n_wg, size_t lds_bytes,
                             hipStream_t st) {
+    if (fast_plan_has_narrow(P, true)) return hipErrorInvalidValue;  // (a narrow twin: k_scan_packed's aggregation columns only)
     if (ng < 0 || ng > kFastMaxG || na < 0 || na > kFastTemplatedA) return hipErrorInvalidValue;
     switch (nf) {
     case 0: return launch_scan_fast_nf0(P, ng, na, mode, time, gen, n_wg, lds_bytes, st);
@@ -28,6 +29,7 @@ hipError_t launch_scan_fast(const FastPlan &P, int nf, int ng, int na, int mode,
 }
 
 hipError_t launch_count(const EmitPlan &E, int nf, int ng, int n_wg, hipStream_t st) {
+    if (fast_plan_has_narrow(E.fp, true)) return hipErrorInvalidValue;  // (a narrow twin: k_scan_packed's aggregation columns only)
     switch (nf) {
     case 0: return launch_count_nf0(E, ng, n_wg, st);
     case 1: return launch_count_nf1(E, ng, n_wg, st);
@@ -39,6 +41,7 @@ hipError_t launch_count(const EmitPlan &E, int nf, int ng, int n_wg, hipStream_t
 }
 
 hipError_t launch_emit(const EmitPlan &E, int nf, int ng, int na, int n_wg, hipStream_t st) {
+    if (fast_plan_has_narrow(E.fp, true)) return hipErrorInvalidValue;  // (a narrow twin: k_scan_packed's aggregation columns only)
     switch (nf) {
     case 0: return launch_emit_nf0(E, ng, na, n_wg, st);
     case 1: return launch_emit_nf1(E, ng, na, n_wg, st);

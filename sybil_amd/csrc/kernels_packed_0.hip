@@ -14,6 +14,7 @@ hipError_t launch_scan_packed_nf0(const FastPlan &P, int ng, int na, int mode, b
 }
 
 hipError_t launch_count_packed(const EmitPlan &E, int nf, int ng, int n_wg, hipStream_t st) {
+    if (fast_plan_has_narrow(E.fp, true)) return hipErrorInvalidValue;  // (a narrow twin: k_scan_packed's aggregation columns only)
     switch (nf) {
     case 0: return launch_count_packed_nf0(E, ng, n_wg, st);
     case 1: return launch_count_packed_nf1(E, ng, n_wg, st);
@@ -25,6 +26,7 @@ hipError_t launch_count_packed(const EmitPlan &E, int nf, int ng, int n_wg, hipS
 }
 
 hipError_t launch_emit_packed(const EmitPlan &E, int nf, int ng, int na, int n_wg, hipStream_t st) {
+    if (fast_plan_has_narrow(E.fp, true)) return hipErrorInvalidValue;  // (a narrow twin: k_scan_packed's aggregation columns only)
     switch (nf) {
     case 0: return launch_emit_packed_nf0(E, ng, na, n_wg, st);
     case 1: return launch_emit_packed_nf1(E, ng, na, n_wg, st);
@@ -37,6 +39,7 @@ hipError_t launch_emit_packed(const EmitPlan &E, int nf, int ng, int na, int n_w
 
 hipError_t launch_scan_packed(const FastPlan &P, int nf, int ng, int na, int mode, bool time, int n_wg, size_t lds_bytes,
                               hipStream_t st) {
+    if (fast_plan_has_narrow(P, false)) return hipErrorInvalidValue;  // (a narrow twin anywhere but an aggregation column)
     if (ng < 0 || ng > kFastMaxG || na < 0 || na > kFastTemplatedA) return hipErrorInvalidValue;
     switch (nf) {
     case 0: return launch_scan_packed_nf0(P, ng, na, mode, time, n_wg, lds_bytes, st);

@@ -1715,6 +1715,36 @@ struct Planner {
                     want ? q->piece_cap : 0, (long long)max_lane_rows());
     }
 
+    // Narrow twins (Column::narrow; table.cpp: column_build_narrow): once the strategy is final and the launch is k_scan_packed's
+    // -- plain, windowed, NUL, static or dynamic -- every aggregation column that has (or can get) a twin is read from it: 3 bytes
+    // a row instead of 4.  The twin keeps the column's base, so abase / adoff / the proofs of plan_count_packing and plan_lean
+    // stand as they are; validity words stay the column's.  Filter, key and time columns, and every other kernel that reads
+    // FastPlan / EmitPlan widths (hash, pushdown, count / emit, the pre-pass, GEN), keep the stored column.
+    // SYBL_PLAN_TRACE=1: `narrow: a0=3 a1=3 bytes_per_row=14` -- the width each aggregation is read at and the bytes a row costs.
+    void plan_narrow() {
+        if (!(q->fast && q->fast_packed && !q->fast_packed_n && !q->hash_mode && !q->part_hist)) return;
+        FastPlan &FP = q->fplan;
+        for (int a = 0; a < q->fast_na; a++) {
+            Column *c = t->cols[(size_t)q->aggs[(size_t)a].col].get();
+            if (FP.awid[a] != 4 || (const void *)FP.acol[a] != c->d_data || FP.abase[a] != c->vbase) continue;
+            if (Column *n = column_build_narrow(t, c)) {
+                FP.acol[a] = (const int64_t *)n->d_data;
+                FP.awid[a] = n->elem;
+            }
+        }
+        if (env("SYBL_PLAN_TRACE")) {
+            int bytes = q->time_mode ? FP.twid : 0;
+            for (int c = 0; c < q->fast_nf; c++) bytes += FP.fwid[c];
+            for (int c = 0; c < q->fast_ng; c++) bytes += FP.gwid[c];
+            std::string line = "narrow:";
+            for (int a = 0; a < q->fast_na; a++) {
+                bytes += FP.awid[a];
+                line += " a" + std::to_string(a) + "=" + std::to_string(FP.awid[a]);
+            }
+            fprintf(stderr, "%s bytes_per_row=%d\n", line.c_str(), bytes);
+        }
+    }
+
     // -limit pushed into the scan (pushdown.hip).  Taken when the caller said the rows beyond the limit need nothing but their
     // Count (printed_only = 2), the query is one strategy 5 runs in a single pass over compact storage with ONE key column
     // and no filter, and the order is $COUNT descending.  The ranks of a job agree on the printed cells before pass 2: the
@@ -1840,6 +1870,7 @@ struct Planner {
         if ((rc = select_part_hist(t, q, slot_col, rows_scanned))) return rc;
         plan_dynamic();  // (plan_count_packing and plan_lean, for the dealing it takes)
         if ((rc = plan_pushdown())) return rc;
+        plan_narrow();
         q->stats.rows_scanned = rows_scanned;
         q->stats.blocks_skipped = skipped;
         q->stats.blocks_scanned = (int64_t)t->blocks.size() - skipped;

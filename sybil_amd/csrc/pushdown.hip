@@ -343,6 +343,7 @@ __global__ __launch_bounds__(kWgThreads, 4) void k_pd_scan(const PushdownPlan D)
 // MAX section with INT64_MIN
 // pass 1: every group's count (D.cnt; the cells' Count fields)
 hipError_t launch_pushdown_count(const PushdownPlan &D, hipStream_t st) {
+    if (fast_plan_has_narrow(D.fp, true)) return hipErrorInvalidValue;  // (a narrow twin: k_scan_packed's aggregation columns only)
     const uint32_t words = ((uint32_t)D.n_cells + 1u) >> 1;
     const size_t lds1 = (size_t)words * 4;
     hipError_t e;
@@ -367,6 +368,7 @@ hipError_t launch_pushdown_count(const PushdownPlan &D, hipStream_t st) {
 
 // the printed cells from D.cnt (across ranks: the all-reduced counts), then pass 2
 hipError_t launch_pushdown_scan(const PushdownPlan &D, hipStream_t st) {
+    if (fast_plan_has_narrow(D.fp, true)) return hipErrorInvalidValue;  // (a narrow twin: k_scan_packed's aggregation columns only)
     hipError_t e;
     hipLaunchKernelGGL(k_pd_select, dim3(1), dim3(1024), 0, st, D);
     hipLaunchKernelGGL(k_pd_clear, dim3((unsigned)std::max(D.limit, 1)), dim3(256), 0, st, D);

@@ -132,6 +132,17 @@ struct FastPlan {
 hipError_t launch_scan_fast(const FastPlan &P, int nf, int ng, int na, int mode, bool time, bool gen, int n_wg,
                             size_t lds_bytes, hipStream_t st);
 
+// A width of 3 is a narrow twin (narrow3.h), which only k_scan_packed decodes, and only as an aggregation column (planner.cpp:
+// plan_narrow).  Every other launcher that takes FastPlan widths refuses a plan that holds one (aggs = true), and
+// launch_scan_packed one that holds it anywhere else: an internal error, never a wrong answer.
+inline bool fast_plan_has_narrow(const FastPlan &P, bool aggs) {
+    bool any = P.twid == 3 || P.wwid == 3;
+    for (int c = 0; c < kFastMaxF; c++) any = any || P.fwid[c] == 3;
+    for (int c = 0; c < kFastMaxG; c++) any = any || P.gwid[c] == 3;
+    for (int c = 0; aggs && c < kFastMaxA; c++) any = any || P.awid[c] == 3;
+    return any;
+}
+
 // ---- FastPlan::lean: the lean row bodies of k_scan_packed (scan_packed.h), taken on the planner's proofs over the EXACT
 // extrema of the resident rows (planner.cpp: plan_lean).
 //

@@ -13,6 +13,7 @@
 // Cell table, LDS layout, publication and fold are those of k_scan_fast (scan_fast.h), so the
 // all-reduce and finalize do not care which kernel ran.
 #pragma once
+#include "narrow3.h"
 #include "scan_fast.h"
 
 namespace sybl {
@@ -69,6 +70,14 @@ __device__ __forceinline__ void packed_issue(const uint8_t *col, int wshift, uin
         __builtin_amdgcn_make_buffer_rsrc((void *)col, 0, (int)((64u * kPackedRows) << wshift), (int)kBufferRsrcWord3);
     raw = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, 0, 2);  // aux 2 = nt: streamed once
 }
+// The same for k_scan_packed, where an aggregation column may be a narrow twin (narrow3.h: 3 bytes a row): address, record
+// count and lane offset are PRODUCTS of the width -- every lane's offset stays a multiple of 4 bytes, the wave's 256 rows are
+// 768, and the last lane's fourth dword is out of range and dropped like a 2-byte column's upper half.
+__device__ __forceinline__ void packed_issue_w(const uint8_t *col, uint32_t width, uint32_t voff, pu32x4 &raw) {
+    const __amdgpu_buffer_rsrc_t rsrc =
+        __builtin_amdgcn_make_buffer_rsrc((void *)col, 0, (int)((64u * kPackedRows) * width), (int)kBufferRsrcWord3);
+    raw = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)voff, 0, 2);  // aux 2 = nt: streamed once
+}
 
 __device__ __forceinline__ void packed_decode(int width, const pu32x4 &raw, uint32_t (&u)[kPackedRows]) {
     if (width == 4) {
@@ -81,6 +90,9 @@ __device__ __forceinline__ void packed_decode(int width, const pu32x4 &raw, uint
         u[1] = raw.x >> 16;
         u[2] = raw.y & 0xFFFFu;
         u[3] = raw.y >> 16;
+    } else if (width == kNarrowWidth) {
+        const uint32_t d[3] = {raw.x, raw.y, raw.z};
+        unpack3(d, u);
     } else {
         u[0] = raw.x & 0xFFu;
         u[1] = (raw.x >> 8) & 0xFFu;
@@ -125,8 +137,8 @@ __device__ __forceinline__ void packed_issue_all(const FastPlan &P0, const Packe
         for (int c = 0; c < NA; c++) a.pw[c] = P.avalid[c] ? P.avalid[c][w] : 0xFFFFFFFFu;
     }
     auto issue = [&](const uint8_t *col, int width, pu32x4 &raw) {
-        const int ws = width >> 1;  // width 1, 2, 4 -> shift 0, 1, 2
-        packed_issue(col + ((size_t)r0 << ws), ws, lane_row << ws, raw);
+        const uint32_t w = (uint32_t)width;  // (r0 < 2^28 + 2^14 rows of at most 4 bytes: the products fit 32 bits)
+        packed_issue_w(col + (size_t)(r0 * w), w, __umul24(lane_row, w), raw);
     };
     if (TIME) issue(B.t, P.twid, t.v[0]);
 #pragma unroll
@@ -157,10 +169,10 @@ __device__ __forceinline__ void packed_issue_always(const FastPlan &P, const Pac
     // only partly inside), which never reaches past the padding every block ends with
     const uint32_t rows = r0 < n ? (n - r0 < 64u * kPackedRows ? (n - r0 + kPackedRows - 1) & ~(uint32_t)(kPackedRows - 1) : 64u * kPackedRows) : 0u;
     auto issue = [&](const uint8_t *col, int width, pu32x4 &raw) {
-        const int ws = width >> 1;  // width 1, 2, 4 -> shift 0, 1, 2
+        const uint32_t w = (uint32_t)width;  // (products of the width: packed_issue_w)
         const __amdgpu_buffer_rsrc_t rsrc =
-            __builtin_amdgcn_make_buffer_rsrc((void *)(col + ((size_t)(rows ? r0 : 0u) << ws)), 0, (int)(rows << ws), (int)kBufferRsrcWord3);
-        raw = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(lane_row << ws), 0, 2);  // aux 2 = nt: streamed once
+            __builtin_amdgcn_make_buffer_rsrc((void *)(col + (size_t)((rows ? r0 : 0u) * w)), 0, (int)(rows * w), (int)kBufferRsrcWord3);
+        raw = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(__umul24(lane_row, w)), 0, 2);  // aux 2 = nt: streamed once
     };
 #pragma unroll
     for (int c = 0; c < NF; c++) issue(B.f[c], P.fwid[c], f.v[c]);
@@ -181,10 +193,10 @@ __device__ __forceinline__ void packed_issue_ring(const FastPlan &P, const Packe
     const uint32_t rows = r0 < n ? (n - r0 < 64u * kPackedRows ? (n - r0 + kPackedRows - 1) & ~(uint32_t)(kPackedRows - 1) : 64u * kPackedRows) : 0u;
     const uint32_t base_row = rows ? r0 : 0u;
     auto issue = [&](const uint8_t *col, int width, pu32x4 &raw) {
-        const int ws = width >> 1;  // width 1, 2, 4 -> shift 0, 1, 2
+        const uint32_t w = (uint32_t)width;  // (products of the width: packed_issue_w)
         const __amdgpu_buffer_rsrc_t rsrc =
-            __builtin_amdgcn_make_buffer_rsrc((void *)(col + ((size_t)base_row << ws)), 0, (int)(rows << ws), (int)kBufferRsrcWord3);
-        raw = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(lane_row << ws), 0, 2);  // aux 2 = nt: streamed once
+            __builtin_amdgcn_make_buffer_rsrc((void *)(col + (size_t)(base_row * w)), 0, (int)(rows * w), (int)kBufferRsrcWord3);
+        raw = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(__umul24(lane_row, w)), 0, 2);  // aux 2 = nt: streamed once
     };
     if (TIME) issue(B.t, P.twid, t.v[0]);
 #pragma unroll
@@ -581,11 +593,11 @@ __device__ __forceinline__ void packed_scan_dyn(const FastPlan &P, int64_t *lds,
                                   ? (T.rows - wave_row < 64u * kPackedRows ? (T.rows - wave_row + kPackedRows - 1) & ~(uint32_t)(kPackedRows - 1) : 64u * kPackedRows)
                                   : 0u;
         const int64_t base = rows ? T.R + wave_row : 0;
-        const int ws = width >> 1;  // width 1, 2, 4 -> shift 0, 1, 2
+        const uint32_t w = (uint32_t)width;  // (products of the width, packed_issue_w; the base is a physical row: 64 bits)
         const __amdgpu_buffer_rsrc_t rsrc =
-            __builtin_amdgcn_make_buffer_rsrc((void *)((const uint8_t *)col + ((size_t)base << ws)), 0, (int)(rows << ws), (int)kBufferRsrcWord3);
+            __builtin_amdgcn_make_buffer_rsrc((void *)((const uint8_t *)col + (size_t)base * w), 0, (int)(rows * w), (int)kBufferRsrcWord3);
         if (one_dword) raw.x = __builtin_amdgcn_raw_buffer_load_b32(rsrc, (int)lane_row, 0, 2);  // (G1: width 1, see packed_issue1)
-        else raw = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(lane_row << ws), 0, 2);     // aux 2 = nt: streamed once
+        else raw = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(__umul24(lane_row, w)), 0, 2);       // aux 2 = nt: streamed once
     };
     auto issue_filters = [&](const DynTile &T) {
 #pragma unroll
@@ -797,9 +809,9 @@ __global__ __launch_bounds__(kWgThreads, SYBL_PACKED_WAVES_PER_EU) void k_scan_p
                     rows = wanted ? rows : 0u;  // (wave-uniform: nothing of this tile is wanted -> a descriptor of zero records)
                     const uint32_t base_row = rows ? r0 : 0u;
                     auto issue = [&](const uint8_t *col, int width, pu32x4 &raw) {
-                        const int ws = width >> 1;
-                        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)(col + ((size_t)base_row << ws)), 0, (int)(rows << ws), (int)kBufferRsrcWord3);
-                        raw = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(lane_row << ws), 0, 2);
+                        const uint32_t w = (uint32_t)width;  // (products of the width: packed_issue_w)
+                        const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)(col + (size_t)(base_row * w)), 0, (int)(rows * w), (int)kBufferRsrcWord3);
+                        raw = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(__umul24(lane_row, w)), 0, 2);
                     };
                     if (TIME) issue(B.t, P.twid, rt.v[0]);
 #pragma unroll
@@ -924,10 +936,10 @@ __device__ __forceinline__ void packed_issue_clamped(const uint8_t *col, int wid
     const uint32_t r0 = __builtin_amdgcn_readfirstlane(r);
     const uint32_t lane_row = r - r0;
     const uint32_t rows = wanted && r0 < n ? (n - r0 < 64u * kPackedRows ? (n - r0 + kPackedRows - 1) & ~(uint32_t)(kPackedRows - 1) : 64u * kPackedRows) : 0u;
-    const int ws = width >> 1;
+    const uint32_t w = (uint32_t)width;  // (products of the width: packed_issue_w)
     const __amdgpu_buffer_rsrc_t rsrc =
-        __builtin_amdgcn_make_buffer_rsrc((void *)(col + ((size_t)(rows ? r0 : 0u) << ws)), 0, (int)(rows << ws), (int)kBufferRsrcWord3);
-    raw = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(lane_row << ws), 0, 2);
+        __builtin_amdgcn_make_buffer_rsrc((void *)(col + (size_t)((rows ? r0 : 0u) * w)), 0, (int)(rows * w), (int)kBufferRsrcWord3);
+    raw = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(__umul24(lane_row, w)), 0, 2);
 }
 
 // LATE (round 6, a kernel of its own -- two loops in one body wreck the other's register allocation): the filter

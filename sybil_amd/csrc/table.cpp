@@ -203,6 +203,7 @@ void column_free(Column *c) {
         c->rank_col.reset();
     }
     c->carried_weight.reset();  // (queries that weigh by it keep their share)
+    column_drop_narrow(c);
     if (c->d_data) hipFree(c->d_data);
     if (c->d_valid) hipFree(c->d_valid);
     if (c->d_set_off) hipFree(c->d_set_off);
@@ -841,6 +842,100 @@ int column_build_rank(Table *t, Column *c) {
     return SYBL_OK;
 }
 
+// ------------------------------------------------------------------ narrow twins (Column::narrow, narrow3.h)
+void column_drop_narrow(Column *c) {
+    if (!c->narrow) return;
+    column_free(c->narrow.get());  // (its d_valid is never set: validity is the parent's)
+    c->narrow.reset();
+    c->narrow_rows = 0;
+    c->narrow_version = -1;
+    c->narrow_blocks = 0;
+}
+
+// SYBL_NARROW_MIN_ROWS (default 2^25 physical rows): below it a twin saves a scan under 5 us per column at HBM speed -- launch
+// noise -- for a pass over the column and 3 B/row of HBM.  SYBL_NO_NARROW=1: no plan reads a twin (the same-binary A/B switch).
+// SYBL_PLAN_TRACE=1: `narrow twin: col=.. rows=.. converted=.. bytes=..` when rows were converted, `.. freed` when one went.
+Column *column_build_narrow(Table *t, Column *c) {
+    int64_t min_rows = (int64_t)1 << 25;
+    if (const char *e = env("SYBL_NARROW_MIN_ROWS")) min_rows = std::max<int64_t>(atoll(e), 1);
+    const bool current = c->narrow && c->narrow_version == t->version;
+    if (env("SYBL_NO_NARROW") || t->phys_rows < min_rows) {
+        // (a twin of this version may be what another prepared query scans: it stays, this plan just does not read it)
+        if (c->narrow && !current) column_drop_narrow(c);
+        return nullptr;
+    }
+    if (current) return c->narrow.get();
+    const bool trace = env("SYBL_PLAN_TRACE") != nullptr;
+    // eligibility from the EXACT extrema (declared bounds say nothing about the stored bits)
+    if (table_ensure_stats(t) != SYBL_OK) return nullptr;
+    const bool eligible = c->type == SYBL_INT_VAL && c->elem == 4 && c->d_data && c->n_pop > 0 && c->exact_min >= c->vbase &&
+                          (unsigned __int128)((__int128)c->exact_max - (__int128)c->vbase) < (unsigned __int128)kNarrowLimit;
+    if (!eligible) {
+        if (c->narrow) {
+            column_drop_narrow(c);
+            if (trace) fprintf(stderr, "narrow twin: col=%s freed\n", c->name.c_str());
+        }
+        return nullptr;
+    }
+    // What changed since the twin was last checked.  Every block_commit adds one block and one to the version, and every other
+    // change of the table (a dropped tail, rows closing up, a reload, bounds, dictionaries) moves the version without adding a
+    // block: the versions differ by exactly the blocks added iff blocks were appended and nothing else happened -- the rows the
+    // twin covers are then what they were, and only the rows beyond them are converted.  A repack or another base shows in
+    // elem (checked above) and vbase.  Anything else: the twin is built again from the first row.
+    int64_t from = 0;
+    if (c->narrow && c->narrow->vbase == c->vbase && c->narrow_rows <= t->phys_rows && (int64_t)t->blocks.size() >= c->narrow_blocks &&
+        t->version - c->narrow_version == (int64_t)t->blocks.size() - c->narrow_blocks)
+        from = c->narrow_rows & ~(int64_t)3;  // (the quad the old last row shares with the first new one is written again)
+    if (from == 0 && c->narrow) column_drop_narrow(c);
+    hipStream_t st = t->ctx->stream;
+    auto give_up = [&]() -> Column * {
+        (void)hipGetLastError();  // an allocation that failed is no error of the query: it plans on the 4-byte column
+        column_drop_narrow(c);
+        return nullptr;
+    };
+    if (load_sync_all(t->ctx) != SYBL_OK) return give_up();
+    if (!c->narrow) {
+        c->narrow = std::make_unique<Column>();
+        c->narrow->name = c->name;
+        c->narrow->type = SYBL_INT_VAL;
+        c->narrow->elem = kNarrowWidth;
+        c->narrow->vbase = c->vbase;
+    }
+    Column *r = c->narrow.get();
+    const int64_t need = t->phys_rows + kTileRows;  // (+ a tile, like table_reserve: the scan's descriptors end on whole lanes)
+    if (need > r->cap_rows) {
+        // (not table_reserve: it copies Table::phys_rows rows of the old array, and the old twin holds narrow_rows)
+        const int64_t cap = std::max(need, std::min(c->cap_rows, r->cap_rows + r->cap_rows / 2));
+        void *nd = nullptr;
+        if (hipMalloc(&nd, (size_t)cap * kNarrowWidth) != hipSuccess) return give_up();
+        if (r->d_data && from > 0) {
+            if (hipMemcpyAsync(nd, r->d_data, (size_t)from * kNarrowWidth, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+                hipStreamSynchronize(st) != hipSuccess) {
+                (void)hipFree(nd);
+                return give_up();
+            }
+        }
+        if (r->d_data) (void)hipFree(r->d_data);
+        r->d_data = nd;
+        r->cap_rows = cap;
+    }
+    hipError_t e = launch_narrow3(c->d_data, r->d_data, from, t->phys_rows - from, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return give_up();
+    r->has_missing = c->has_missing;
+    r->n_pop = c->n_pop;
+    r->exact_min = c->exact_min;
+    r->exact_max = c->exact_max;
+    r->stats_blocks = (int64_t)t->blocks.size();
+    if (trace)
+        fprintf(stderr, "narrow twin: col=%s rows=%lld converted=%lld bytes=%lld\n", c->name.c_str(), (long long)t->phys_rows,
+                (long long)(t->phys_rows - from), (long long)(r->cap_rows * kNarrowWidth));
+    c->narrow_rows = t->phys_rows;
+    c->narrow_version = t->version;
+    c->narrow_blocks = (int64_t)t->blocks.size();
+    return r;
+}
+
 int column_upload_set(Table *t, Column *c) {
     if (c->type != SYBL_SET_VAL || !c->set_dirty) return SYBL_OK;
     // offsets for every physical row + the scan's one-tile slack
@@ -1035,6 +1130,7 @@ int64_t sybl_table_hbm_bytes(const sybl_table *t) {
         // ... and the columns derived from it: a sparse key's rank column, a weight column's carried weights
         if (c->rank_col) b += c->rank_col->cap_rows * c->rank_col->elem;
         if (c->carried_weight) b += c->carried_weight->cap_rows * c->carried_weight->elem;
+        if (c->narrow) b += c->narrow->cap_rows * c->narrow->elem;  // ... a 4-byte column's narrow twin
     }
     return b;
 }

@@ -4,6 +4,9 @@
 //            and one dword per 1-byte column)
 //   R = 8  : 4-byte columns two dwordx4 per lane (lane stride 32 B), 2-byte one dwordx4, 1-byte one dwordx2
 //   R = 16 : 4-byte four dwordx4 (lane stride 64 B), 2-byte two, 1-byte one
+// and, at R = 4, the same mix with the two 4-byte columns stored at 3 bytes per row (14 B/row, k_loads_narrow): a dwordx4 at a
+// 12-byte lane stride behind a 768-byte descriptor (the fourth dword of lane 63 is range-checked away), or a dwordx3.  These
+// run in turns against the 16 B mix and print min / median / max, so the two ranges can be set side by side.
 // build: hipcc --offload-arch=gfx950 -O3 -o loadpat loadpat.hip ; run: ./loadpat [rows]
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,6 +14,7 @@
 #include <stdlib.h>
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
+typedef unsigned int u32x3 __attribute__((ext_vector_type(3)));
 struct Cols { const uint8_t *c[7]; int w[7]; };
 constexpr int kThreads = 1024;
 
@@ -55,6 +59,31 @@ __global__ __launch_bounds__(kThreads) void k_loads(Cols C, int64_t rows, uint32
     if (acc == 0x12345678u) out[0] = acc;
 }
 
+// R = 4 with the two aggregation columns AW bytes wide (4: today's mix, 3: the narrow twins); X3: a dwordx3 for the 3-byte columns
+template <int AW, bool X3>
+__global__ __launch_bounds__(kThreads) void k_loads_narrow(Cols C, int64_t rows, uint32_t *out) {
+    const int64_t per_wg = (rows / gridDim.x) / (kThreads * 4) * (kThreads * 4);
+    const int64_t start = (int64_t)blockIdx.x * per_wg;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t acc = 0;
+    for (int64_t t = 0; t < per_wg; t += kThreads * 4) {
+        const int64_t wave_row = start + t + (int64_t)wave * 256;
+#pragma unroll
+        for (int c = 0; c < 7; c++) {
+            const int w = c < 3 ? 2 : c < 5 ? 1 : AW;
+            const uint8_t *base = C.c[c] + wave_row * w;
+            const uint32_t wave_bytes = 256u * w, off = lane * 4 * w;
+            if (w == 1) acc ^= load_lane<4>(base, wave_bytes, off);
+            else if (w == 3 && X3) {
+                const __amdgpu_buffer_rsrc_t rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)base, 0, (int)wave_bytes, 0x00020000);
+                u32x3 v = __builtin_amdgcn_raw_buffer_load_b96(rsrc, (int)off, 0, 2);
+                acc ^= v.x ^ v.y ^ v.z;
+            } else acc ^= load_lane<16>(base, wave_bytes, off);
+        }
+    }
+    if (acc == 0x12345678u) out[0] = acc;
+}
+
 int main(int argc, char **argv) {
     const int64_t rows = argc > 1 ? atoll(argv[1]) : 1000000000LL;
     Cols C;
@@ -89,6 +118,31 @@ int main(int argc, char **argv) {
         run("R=4 exact (dwordx2 for 2-byte)", k_loads<4, false>, wgs);
         run("R=8", k_loads<8, false>, wgs);
         run("R=16", k_loads<16, false>, wgs);
+    }
+    // the 16 B mix against the 14 B mix, in turns: one launch of each per turn, the first turn dropped
+    for (int wgs : {256, 512}) {
+        const int kTurns = 11;
+        float ms[3][kTurns];
+        for (int it = 0; it < kTurns; it++)
+            for (int v = 0; v < 3; v++) {
+                hipEventRecord(e0);
+                if (v == 0) hipLaunchKernelGGL((k_loads_narrow<4, false>), dim3(wgs), dim3(kThreads), 0, 0, C, rows, out);
+                if (v == 1) hipLaunchKernelGGL((k_loads_narrow<3, false>), dim3(wgs), dim3(kThreads), 0, 0, C, rows, out);
+                if (v == 2) hipLaunchKernelGGL((k_loads_narrow<3, true>), dim3(wgs), dim3(kThreads), 0, 0, C, rows, out);
+                hipEventRecord(e1);
+                hipEventSynchronize(e1);
+                hipEventElapsedTime(&ms[v][it], e0, e1);
+            }
+        const char *names[3] = {"16 B mix (4-byte agg, dwordx4)", "14 B mix (3-byte agg, dwordx4)", "14 B mix (3-byte agg, dwordx3)"};
+        for (int v = 0; v < 3; v++) {
+            float *m = ms[v] + 1;
+            for (int i = 0; i < kTurns - 1; i++)
+                for (int j = i + 1; j < kTurns - 1; j++)
+                    if (m[j] < m[i]) { float t = m[i]; m[i] = m[j]; m[j] = t; }
+            const double b = v == 0 ? 16.0 : 14.0;
+            printf("%-34s wgs %4d  min %.3f  med %.3f  max %.3f ms  %.0f GB/s of %.0f B/row at the median\n", names[v], wgs, m[0],
+                   m[(kTurns - 1) / 2], m[kTurns - 2], rows * b / (m[(kTurns - 1) / 2] * 1e-3) / 1e9, b);
+        }
     }
     return 0;
 }
