@@ -834,6 +834,84 @@ typedef struct {
 } sybl_lookup_stats;
 int sybl_table_lookup_stats(const sybl_table *t, sybl_lookup_stats *out);
 
+/* ------------------------------------------------------------------ compute
+ * INT columns computed from expressions over a table's columns, as a NEW resident table: the projection that makes a new value
+ * (latency = end - start, is_error = status >= 500, hour = time % 86400 / 3600, coalesce(region_id, 0)).  Queries group, filter
+ * and aggregate over stored columns only; this call stores the value once, at the narrowest width that holds its ACTUAL range,
+ * and everything behind it is a plain scan of a resident table.  The reference has no such call: the semantics are this
+ * library's.  Evaluation, extrema and storage run on the GPU (csrc/compute.hip).  Restated deterministically:
+ *   rows, blocks and the columns of t: exactly what sybl_table_concat of t alone gives -- t's live non-empty blocks in resident
+ *     order, block boundaries kept, each block starting on a multiple of 32 physical rows; the columns of t come out as that
+ *     concat gives them (values, dictionaries, storage, validity, statistics, and the list of what is not inherited).  The
+ *     computed columns follow t's columns in the order given.  Expression k is evaluated on the OUTPUT's columns row by row, so it
+ *     may name computed columns 0 .. k-1.  t without rows: all the columns (computed ones included), no blocks, no kernel runs.
+ *   expressions: the result is always an INT column.
+ *     literals: decimal digits, value <= 2^63; 9223372036854775808 wraps to INT64_MIN so that -9223372036854775808 can be written.
+ *     columns: a name [A-Za-z_][A-Za-z0-9_]*, or any name between backticks; a name followed by ( is a function.  A column read
+ *       as a value must be an INT column of the output; STR and SET columns may appear only as the argument of has().
+ *     operators, C precedence, the binary ones left-associative: unary - !   * / %   + -   < <= > >=   == !=   &&   ||   and
+ *       parentheses.  Functions: min(a,b) max(a,b) abs(a) if(c,a,b) coalesce(a,b) has(col).
+ *     values: signed 64-bit integers with Go's semantics.  + - * unary - and abs wrap mod 2^64; / truncates toward zero; % takes
+ *       the dividend's sign; INT64_MIN / -1 == INT64_MIN and INT64_MIN % -1 == 0.  Comparisons, ! && || give 1 or 0; truth is
+ *       != 0.
+ *     populated or not: a column operand is unpopulated where its validity bit is clear.  An operator or function with an
+ *       unpopulated operand gives an unpopulated result -- && and || included: both sides are always evaluated, nothing
+ *       short-circuits.  / and % by a populated zero give an unpopulated result (Go would panic; this call does not).
+ *       if(c,a,b) is unpopulated where c is; elsewhere it takes the value AND the populatedness of the chosen branch only (a zero
+ *       divisor in the other branch does not matter).  coalesce(a,b) is a where a is populated, else b with b's populatedness.
+ *       has(col) is 1 or 0, always populated: for any column type the bit sybl_samples_column reports as `populated`.
+ *     limits, each SYBL_E_INVAL: more than 8 distinct columns per expression (the filters' limit), more than 64 postfix ops, an
+ *       operand stack deeper than 8, parentheses or calls nested deeper than 64.
+ *     not in the language: bit operators and shifts, string-valued expressions, set membership, anything floating point.
+ *   each computed column: type INT; no IntInfo (the exact extrema are in force); no dictionary; no declared bounds.  It is
+ *     populated exactly where the expression is; the stored bytes are 0 where it is unpopulated and in padding rows.  has_missing
+ *     is true iff some live row is unpopulated, and it has a validity bitmap iff some live row is unpopulated (padding bits zero).
+ *   storage: compact iff the output is in compact mode (iff t is).  In compact mode the column is stored at the narrowest of
+ *     1 / 2 / 4 / 8 bytes that holds hi - lo, as offsets from lo, over the EXACT minimum lo and maximum hi of the populated
+ *     results -- concat's rule; with no populated row: width 1, base 0.  Otherwise canonical int64, base 0.
+ *   statistics: per-block min / max / populated counts and the table-wide extrema are exact.
+ * SYBL_E_INVAL, sybl_last_error beginning "sybl_table_compute: " and naming the expression's column (for syntax errors with the
+ * byte offset): NULL t, d, out, exprs, a NULL name or expr; n_exprs < 1; an empty name; a name the output already holds (a column
+ * of t or an earlier computed one); an unknown column; a STR or SET column used as a value; a syntax error; a wrong argument
+ * count; a literal above 2^63; any of the limits.  Everything that can be refused is refused before anything is made; *out is
+ * NULL after any failure.  When HBM runs out: SYBL_E_NOMEM, everything freed.
+ * t is untouched and its version does not move: a query prepared on it before the call still scans afterwards.  The output has
+ * t's ctx and name, is attached to no directory, owns everything it shows and outlives t; free it with sybl_table_free.
+ * Rank-local, never collective; runs on the ctx stream, is complete on return and thread-safe per ctx like select.  There is no
+ * row limit: no row numbers travel.
+ * Out of scope: a CLI flag; fusing an expression into a query's scan; STR or SET results; float results; aggregates or window
+ * functions inside expressions. */
+typedef struct {
+    const char *name;   /* of the computed column */
+    const char *expr;
+} sybl_compute_col;
+typedef struct {
+    int32_t n_exprs;
+    const sybl_compute_col *exprs;
+} sybl_compute_desc;
+
+int sybl_table_compute(sybl_table *t, const sybl_compute_desc *d, sybl_table **out);
+
+/* What the sybl_table_compute that made this table did (zeros for any other table). */
+typedef struct {
+    int64_t rows, blocks;        /* of the output */
+    int32_t exprs, ops;          /* expressions; sum of their program lengths */
+    int64_t unpopulated;         /* sum over the expressions of the live rows whose result is unpopulated */
+    double range_ms, store_ms, stats_ms;   /* hipEvent time: extrema passes; store passes + validity; block statistics */
+    int64_t range_bytes, store_bytes;      /* computed from the shapes */
+} sybl_compute_stats;
+int sybl_table_compute_stats(const sybl_table *t, sybl_compute_stats *out);
+
+/* Test hooks (no GPU needed) for compute expressions: the host build of the parser and of the very op functions the kernel uses
+ * (csrc/compute_expr.h, csrc/compute_ops.h).  names / types: the n_cols columns the expression may name (types[i]: SYBL_INT_VAL /
+ * SYBL_STR_VAL / SYBL_SET_VAL).  sybl_debug_compute_program: the postfix form, e.g. "c0 c1 sub 1000 div" -- c<k> is the k-th
+ * distinct column of the expression, has(c<k>) its populated bit, constants by value, ops by name; NULL (and sybl_last_error) on
+ * a refusal.  Library-owned buffer, valid until the next call on the thread.  sybl_debug_compute_eval: values / populated are
+ * [n_cols][n_rows]; out / out_populated get n_rows results (0 where unpopulated). */
+const char *sybl_debug_compute_program(const char *expr, int32_t n_cols, const char *const *names, const int32_t *types);
+int sybl_debug_compute_eval(const char *expr, int32_t n_cols, const char *const *names, const int32_t *types, const int64_t *values,
+                            const uint8_t *populated, int64_t n_rows, int64_t *out, uint8_t *out_populated);
+
 /* Test hook (no GPU needed): the library's regular-expression engine for re / nre str filters -- Go regexp
  * (RE2) syntax, unanchored search like regexp.MatchString (filter.go:213-236).  1 = match, 0 = no match,
  * -1 = the pattern does not compile (sybl_last_error says why). */

@@ -170,6 +170,23 @@ class LookupStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class ComputeCol(C.Structure):
+    _fields_ = [("name", C.c_char_p), ("expr", C.c_char_p)]
+
+
+class ComputeDesc(C.Structure):
+    _fields_ = [("n_exprs", C.c_int32), ("exprs", C.POINTER(ComputeCol))]
+
+
+class ComputeStats(C.Structure):
+    _fields_ = [("rows", C.c_int64), ("blocks", C.c_int64), ("exprs", C.c_int32), ("ops", C.c_int32), ("unpopulated", C.c_int64),
+                ("range_ms", C.c_double), ("store_ms", C.c_double), ("stats_ms", C.c_double), ("range_bytes", C.c_int64),
+                ("store_bytes", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol include/sybilgpu.h declares: (restype, argtypes)
 P = C.c_void_p
 SIGNATURES = {
@@ -256,6 +273,10 @@ SIGNATURES = {
     "sybl_table_concat_stats": (C.c_int, [P, C.POINTER(ConcatStats)]),
     "sybl_table_lookup": (C.c_int, [P, C.POINTER(LookupDesc), C.POINTER(P)]),
     "sybl_table_lookup_stats": (C.c_int, [P, C.POINTER(LookupStats)]),
+    "sybl_table_compute": (C.c_int, [P, C.POINTER(ComputeDesc), C.POINTER(P)]),
+    "sybl_table_compute_stats": (C.c_int, [P, C.POINTER(ComputeStats)]),
+    "sybl_debug_compute_program": (C.c_char_p, [C.c_char_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]),
+    "sybl_debug_compute_eval": (C.c_int, [C.c_char_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), P, P, C.c_int64, P, P]),
 }
 
 _lib = None

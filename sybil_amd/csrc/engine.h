@@ -219,6 +219,7 @@ struct Table {
     sybl_select_stats select_stats{};  // of the sybl_table_select that made this table (select.hip)
     sybl_concat_stats concat_stats{};  // of the sybl_table_concat that made this table (concat.hip)
     sybl_lookup_stats lookup_stats{};  // of the sybl_table_lookup that made this table (lookup.hip)
+    sybl_compute_stats compute_stats{};  // of the sybl_table_compute that made this table (compute.hip)
     std::string src_dir;           // <dir>/<table> the table was opened from ("" = built through the ABI)
     int src_rank = 0, src_nranks = 1;
     std::vector<LoadedBlock> loaded;
@@ -572,6 +573,7 @@ int digest_run(Table *t, const char *time_col, int32_t block_rows, sybl_table **
 int select_run(Table *t, const sybl_select_desc *d, sybl_table **out);  // select.hip
 int concat_run(const sybl_concat_desc *d, sybl_table **out);  // concat.hip
 int lookup_run(Table *t, const sybl_lookup_desc *d, sybl_table **out);  // lookup.hip
+int compute_run(Table *t, const sybl_compute_desc *d, sybl_table **out);  // compute.hip
 int query_rescan_without_part_hist(Query *q);
 
 constexpr int kMaxScatterRanks = 64;  // the SUM section is padded so that a reduce-scatter over up to this many ranks fits in place

@@ -366,6 +366,27 @@ class Table:
         N.check(N.lib().sybl_table_lookup_stats(self._h, C.byref(st)))
         return st.as_dict()
 
+    def compute(self, exprs):
+        """INT columns computed from expressions over this table's columns, appended to a copy of it as a NEW resident table
+        (sybl_table_compute).  exprs: a list of (name, expr) pairs, or a dict in insertion order; expression k may name the
+        computed columns before it.  `end - start`, `status >= 500`, `time % 86400 / 3600`, `coalesce(region, 0)`, `has(tag)`:
+        the language is restated in include/sybilgpu.h.  This table is untouched; free both."""
+        pairs = list(exprs.items()) if isinstance(exprs, dict) else [tuple(e) for e in exprs]
+        arr = (N.ComputeCol * max(len(pairs), 1))()
+        for i, (name, expr) in enumerate(pairs):
+            arr[i] = N.ComputeCol(_b(name), _b(expr))
+        d = N.ComputeDesc()
+        d.n_exprs, d.exprs = len(pairs), C.cast(arr, C.POINTER(N.ComputeCol))
+        h = C.c_void_p()
+        N.check(N.lib().sybl_table_compute(self._h, C.byref(d), C.byref(h)))
+        return Table(self.ctx, h, self.name)
+
+    def compute_stats(self):
+        """Counts, device time and bytes of the passes of the compute() that made this table (sybl_table_compute_stats)."""
+        st = N.ComputeStats()
+        N.check(N.lib().sybl_table_compute_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
     def query(self, filters=(), groups=(), aggs=(), op="avg", hist_bucket=0, want_percentiles=True, time_col=None,
               time_bucket=0, weight_col=None, order_by="$COUNT", order_asc=False, limit=0, block_skip=False, loghist=False, str_replace=(),
               distincts=(), printed_only=False):
