@@ -22,6 +22,7 @@
 #include "plan.h"
 #include "scan_fast.h"
 #include "scan_packed.h"
+#include "fword.h"
 
 namespace sybl {
 
@@ -64,6 +65,7 @@ hipError_t launch_hist_summary(const HistSummaryPlan &S, int64_t *total, hipStre
 hipError_t launch_rank_column(const void *col, int width, int64_t vbase, const uint32_t *valid, const int64_t *dkeys, const int32_t *dranks, uint32_t dmask,
                               int64_t n, void *out, int ow, uint32_t miss, hipStream_t st);
 hipError_t launch_narrow3(const void *src, void *dst, int64_t row0, int64_t rows, hipStream_t st);
+hipError_t launch_pack_fword(const FwordPack &S, void *dst, int64_t row0, int64_t rows, hipStream_t st);
 hipError_t launch_weight_carry(const void *col, int width, int64_t vbase, const uint32_t *valid, const Segment *d_blocks, int n_blocks, int64_t *out, hipStream_t st);
 hipError_t launch_hist_total(const int64_t *H, int64_t hist_stride, int64_t cell0, int64_t cell1, int64_t *total, hipStream_t st);
 hipError_t launch_hist_gather(const int64_t *H, int64_t hist_stride, const int64_t *d_cells, int64_t n, int64_t cell0, int64_t cell1,
@@ -197,6 +199,28 @@ struct LoadedBlock {
     int64_t index = -1;              // into Table::blocks; -1: skipped as broken / unreadable
 };
 
+// A filter word (fword.h; table.cpp: table_build_fword): the stored offsets of a SET of compact int columns -- the filter
+// columns of a query -- as bit fields of one 4-byte word per row, which k_scan_packed's dynamic loops read in the columns'
+// place: config 3's three 2-byte filters cost 4 bytes a row instead of 6, and one full 16-byte load per lane instead of three
+// half-empty ones.  Derived data like Column::narrow: built once per table version at prepare, shared by the prepared queries
+// that filter by the same columns, counted in sybl_table_hbm_bytes, and invisible to stored widths, algorithmic_bytes and every
+// table-to-table feature.  The table holds at most SYBL_FWORD_MAX of them (Table::fwords, least recently planned first to go)
+// and a prepared query holds its own share (Query::fword): a word that is evicted or replaced is freed by its last holder.
+struct FilterWord {
+    std::vector<int> cols;  // table column indices, ascending: the key, and the order of the fields
+    int n = 0;
+    int32_t bits[kFwordMaxFields] = {}, shift[kFwordMaxFields] = {};
+    int elem[kFwordMaxFields] = {};       // the columns' stored widths and bases the words were packed from
+    int64_t vbase[kFwordMaxFields] = {};
+    void *d_data = nullptr;
+    int64_t cap_rows = 0;
+    int64_t rows = 0, version = -1, blocks = 0;  // the physical rows it covers; valid for (Table::version, blocks) = (version, blocks)
+    uint64_t planned = 0;                        // Table::fword_clock when a plan last took it
+    ~FilterWord() {
+        if (d_data) (void)hipFree(d_data);
+    }
+};
+
 struct Query;
 struct Table {
     Ctx *ctx = nullptr;
@@ -224,6 +248,8 @@ struct Table {
     int src_rank = 0, src_nranks = 1;
     std::vector<LoadedBlock> loaded;
     std::vector<Query *> queries;  // prepared queries that are alive (a table that goes away first has their pending lazy results built)
+    std::vector<std::shared_ptr<FilterWord>> fwords;  // the filter words this table holds (table_build_fword)
+    uint64_t fword_clock = 0;
     Column *find(const char *name) const;
 };
 
@@ -242,6 +268,9 @@ int column_build_rank(Table *t, Column *c);            // Column::rank_col for t
 // (never an error of the query: the plan keeps the 4-byte column)
 Column *column_build_narrow(Table *t, Column *c);
 void column_drop_narrow(Column *c);
+// The filter word of columns cols[0 .. n) (table column indices, any order, no duplicates) for the current table version, or
+// nullptr: the set is not eligible, the feature is off, or HBM is short (never an error of the query: the plan keeps the columns)
+std::shared_ptr<FilterWord> table_build_fword(Table *t, const int *cols, int n);
 int column_install_gdict(Table *t, Column *c);         // sorted gdict -> device value->rank map
 int column_repack(Table *t, Column *c, int width, int64_t vbase);  // change the stored width in place
 
@@ -429,6 +458,7 @@ struct Query {
     // a weight column with unpopulated rows: the weight in force at every row (k_weight_carry), a dense int64 column of this
     // query's own that the scan reads in the weight column's place (planner.cpp: Planner::weight)
     std::shared_ptr<Column> eff_weight;  // (= the weight column's Column::carried_weight)
+    std::shared_ptr<FilterWord> fword;   // the filter word fplan reads (planner.cpp: plan_fword), or none: this query's share of it
     int printed_level = 0;      // sybl_query_desc.printed_only as given (2: the rows beyond the limit may carry their Count alone)
     bool printed_only = false;  // sybl_query_desc.printed_only: percentiles / stddev / bucket arrays for the printed rows + Cumulative only
     bool top_only = false;      // ... and this query is one it applies to (query_snapshot: summary shape, limit > 0)

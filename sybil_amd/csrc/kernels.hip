@@ -28,6 +28,7 @@
 #include "plan.h"
 #include "gob_bins.h"
 #include "narrow3.h"
+#include "fword.h"
 #include "scan_fast.h"
 #include "scan_generic.h"
 
@@ -375,6 +376,51 @@ hipError_t launch_narrow3(const void *src, void *dst, int64_t row0, int64_t rows
     if (row0 & 3) return hipErrorInvalidValue;
     const int64_t quads = (rows + 3) / 4, blocks = (quads + 255) / 256;
     hipLaunchKernelGGL(k_narrow3, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, st, (const uint32_t *)src, (uint32_t *)dst, row0 / 4, quads);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- a filter word (fword.h)
+// The stored offsets of S.n columns as bit fields of one dword per row, for quads [q0, q0 + n): a thread reads its quad of every
+// source column at the column's stored width -- a dword, a dwordx2 or a dwordx4 -- and writes one dwordx4.  Every offset is cut
+// to its field (a row beyond the table's last carries don't-care bits in the columns: they stay inside that row's word).
+__global__ __launch_bounds__(256) void k_pack_fword(const FwordPack S, uint32_t *__restrict__ dst, int64_t q0, int64_t n) {
+    typedef uint32_t quad_t __attribute__((ext_vector_type(4)));
+    typedef uint32_t pair_t __attribute__((ext_vector_type(2)));
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (int64_t)gridDim.x * blockDim.x) {
+        uint32_t w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+        for (int c = 0; c < kFwordMaxFields; c++) {
+            if (c >= S.n) break;
+            uint32_t u[4];
+            if (S.wid[c] == 4) {
+                const quad_t v = __builtin_nontemporal_load((const quad_t *)S.col[c] + (q0 + q));
+                u[0] = v.x, u[1] = v.y, u[2] = v.z, u[3] = v.w;
+            } else if (S.wid[c] == 2) {
+                const pair_t v = __builtin_nontemporal_load((const pair_t *)S.col[c] + (q0 + q));
+                u[0] = v.x & 0xFFFFu, u[1] = v.x >> 16, u[2] = v.y & 0xFFFFu, u[3] = v.y >> 16;
+            } else {
+                const uint32_t v = __builtin_nontemporal_load((const uint32_t *)S.col[c] + (q0 + q));
+                u[0] = v & 0xFFu, u[1] = (v >> 8) & 0xFFu, u[2] = (v >> 16) & 0xFFu, u[3] = v >> 24;
+            }
+            const uint32_t mask = fword_mask(S.bits[c]);
+#pragma unroll
+            for (int k = 0; k < 4; k++) w[k] |= (u[k] & mask) << S.shift[c];
+        }
+        quad_t o;
+        o.x = w[0], o.y = w[1], o.z = w[2], o.w = w[3];
+        __builtin_nontemporal_store(o, (quad_t *)dst + (q0 + q));
+    }
+}
+// rows [row0, row0 + rows) of the columns of S into the word array `dst`; row0 a multiple of 4, and every array holds the whole
+// last quad (every column is reserved a tile beyond its rows: table_reserve)
+hipError_t launch_pack_fword(const FwordPack &S, void *dst, int64_t row0, int64_t rows, hipStream_t st) {
+    if (rows <= 0) return hipSuccess;
+    if ((row0 & 3) || S.n < kFwordMinFields || S.n > kFwordMaxFields) return hipErrorInvalidValue;
+    for (int c = 0; c < S.n; c++)
+        if ((S.wid[c] != 1 && S.wid[c] != 2 && S.wid[c] != 4) || S.bits[c] < 1 || S.shift[c] < 0 || S.shift[c] + S.bits[c] > kFwordBits || !S.col[c])
+            return hipErrorInvalidValue;
+    const int64_t quads = (rows + 3) / 4, blocks = (quads + 255) / 256;
+    hipLaunchKernelGGL(k_pack_fword, dim3((unsigned)(blocks < 16384 ? blocks : 16384)), dim3(256), 0, st, S, (uint32_t *)dst, row0 / 4, quads);
     return hipGetLastError();
 }
 

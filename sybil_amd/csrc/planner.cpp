@@ -1715,15 +1715,49 @@ struct Planner {
                     want ? q->piece_cap : 0, (long long)max_lane_rows());
     }
 
+    // Filter words (Table::fwords, fword.h; table.cpp: table_build_fword): when the launch is k_scan_packed's with the DYNAMIC
+    // loops (packed_scan_dyn -- the static, ring, windowed and NUL kernels keep the columns) and the query has two or more filter
+    // columns, every one a plain range over the stored int column, the filters are read from one 4-byte word per row that holds
+    // the columns' stored offsets as bit fields.  The offsets are the columns': plo / phi (the plo > phi "nothing passes" case
+    // too) and every proof stand as they are.  fcol / fwid / fbase keep the stored columns' values -- hash, pushdown, count / emit,
+    // the pre-pass, samples, select and GEN never see a word.  The word is keyed by the SET of columns; this plan's filter c is
+    // the field of its column, whatever order the query lists them in.
+    void plan_fword() {
+        FastPlan &FP = q->fplan;
+        FP.fword = nullptr;
+        q->fword.reset();
+        if (!q->dyn || FP.nul || q->fast_nf < kFwordMinFields || q->fast_nf > kFwordMaxFields) return;
+        int cols[kFwordMaxFields];
+        for (int c = 0; c < q->fast_nf; c++) {
+            cols[c] = -1;
+            for (size_t i = 0; i < t->cols.size(); i++)
+                if (t->cols[i]->d_data && t->cols[i]->d_data == (const void *)FP.fcol[c]) cols[c] = (int)i;
+            if (cols[c] < 0) return;  // (a derived column -- ranks -- in a filter's place)
+            const Column *col = t->cols[(size_t)cols[c]].get();
+            if (FP.fmask[c] || FP.nneq[c] || FP.npneq[c] || FP.fvalid[c] || FP.fwid[c] != col->elem || FP.fbase[c] != col->vbase) return;
+        }
+        std::shared_ptr<FilterWord> w = table_build_fword(t, cols, q->fast_nf);
+        if (!w) return;
+        for (int c = 0; c < q->fast_nf; c++) {
+            const int i = (int)(std::find(w->cols.begin(), w->cols.end(), cols[c]) - w->cols.begin());
+            FP.fshift[c] = w->shift[i];
+            FP.fbits[c] = w->bits[i];
+        }
+        FP.fword = (const uint32_t *)w->d_data;
+        q->fword = std::move(w);
+    }
+
     // Narrow twins (Column::narrow; table.cpp: column_build_narrow): once the strategy is final and the launch is k_scan_packed's
     // -- plain, windowed, NUL, static or dynamic -- every aggregation column that has (or can get) a twin is read from it: 3 bytes
     // a row instead of 4.  The twin keeps the column's base, so abase / adoff / the proofs of plan_count_packing and plan_lean
     // stand as they are; validity words stay the column's.  Filter, key and time columns, and every other kernel that reads
     // FastPlan / EmitPlan widths (hash, pushdown, count / emit, the pre-pass, GEN), keep the stored column.
-    // SYBL_PLAN_TRACE=1: `narrow: a0=3 a1=3 bytes_per_row=14` -- the width each aggregation is read at and the bytes a row costs.
+    // SYBL_PLAN_TRACE=1: `narrow: a0=3 a1=3 bytes_per_row=14` -- the width each aggregation is read at and the bytes a row costs;
+    // with a filter word (plan_fword) `narrow: f=word(10,10,10) a0=3 a1=3 bytes_per_row=12`.
     void plan_narrow() {
         if (!(q->fast && q->fast_packed && !q->fast_packed_n && !q->hash_mode && !q->part_hist)) return;
         FastPlan &FP = q->fplan;
+        plan_fword();
         for (int a = 0; a < q->fast_na; a++) {
             Column *c = t->cols[(size_t)q->aggs[(size_t)a].col].get();
             if (FP.awid[a] != 4 || (const void *)FP.acol[a] != c->d_data || FP.abase[a] != c->vbase) continue;
@@ -1734,9 +1768,15 @@ struct Planner {
         }
         if (env("SYBL_PLAN_TRACE")) {
             int bytes = q->time_mode ? FP.twid : 0;
-            for (int c = 0; c < q->fast_nf; c++) bytes += FP.fwid[c];
+            for (int c = 0; c < q->fast_nf; c++) bytes += FP.fword ? 0 : FP.fwid[c];
             for (int c = 0; c < q->fast_ng; c++) bytes += FP.gwid[c];
             std::string line = "narrow:";
+            if (FP.fword) {  // (plan_fword) the filters, as the bits of each one's field: `f=word(10,10,10)`
+                bytes += 4;
+                line += " f=word(";
+                for (int c = 0; c < q->fast_nf; c++) line += (c ? "," : "") + std::to_string(FP.fbits[c]);
+                line += ")";
+            }
             for (int a = 0; a < q->fast_na; a++) {
                 bytes += FP.awid[a];
                 line += " a" + std::to_string(a) + "=" + std::to_string(FP.awid[a]);

@@ -127,6 +127,11 @@ struct FastPlan {
     int32_t dyn, n_pieces, piece_cap;
     const Piece *pieces;
     uint32_t *piece_queue;
+    // k_scan_packed's dynamic loops (the FW instantiations; planner.cpp: plan_fword): the filter columns' stored offsets read
+    // from ONE 4-byte word per row (fword.h) -- filter c is the field of fbits[c] bits at fshift[c] -- instead of from fcol[].
+    // nullptr = the columns.  fcol / fwid / fbase stay the stored columns' values: no other kernel ever sees a word.
+    const uint32_t *fword;
+    int32_t fshift[kFastMaxF], fbits[kFastMaxF];
 };
 
 hipError_t launch_scan_fast(const FastPlan &P, int nf, int ng, int na, int mode, bool time, bool gen, int n_wg,

@@ -14,6 +14,7 @@
 // all-reduce and finalize do not care which kernel ran.
 #pragma once
 #include "narrow3.h"
+#include "fword.h"
 #include "scan_fast.h"
 
 namespace sybl {
@@ -570,9 +571,14 @@ struct DynCursor {
     }
 };
 
-template <int NF, int NG, int NA, int MODE, bool TIME, bool G1, int LEANV>
+// FW: the filter columns' offsets come from one filter word per row (FastPlan::fword, fword.h) -- ONE full 16-byte load per lane
+// and tile into rf.v[0] where the columns take NF, and a bit-field extract per column and row where they take a width decode.
+// A property of the kernel like LEANV and DYN (the launcher picks it from P.fword): nothing in the loop asks which it is.
+template <int NF, int NG, int NA, int MODE, bool TIME, bool G1, int LEANV, bool FW>
 __device__ __forceinline__ void packed_scan_dyn(const FastPlan &P, int64_t *lds, const FastLds &L, const bool max32, uint32_t &matched,
                                                 uint32_t &overflow) {
+    static_assert(!FW || NF >= kFwordMinFields, "a filter word holds at least two columns");
+    static_assert(kFwordMaxFields == kFastMaxF, "one field per filter column of a FastPlan");
     __shared__ uint32_t ring[4];
     const uint32_t tid = threadIdx.x;
     const uint32_t wave_row = __builtin_amdgcn_readfirstlane((tid & ~63u) * kPackedRows);  // the wave's first row inside a tile
@@ -600,8 +606,25 @@ __device__ __forceinline__ void packed_scan_dyn(const FastPlan &P, int64_t *lds,
         else raw = __builtin_amdgcn_raw_buffer_load_b128(rsrc, (int)(__umul24(lane_row, w)), 0, 2);       // aux 2 = nt: streamed once
     };
     auto issue_filters = [&](const DynTile &T) {
+        if constexpr (FW) {
+            issue(P.fword, 4, T, true, rf.v[0], false);
+        } else {
 #pragma unroll
-        for (int c = 0; c < NF; c++) issue(P.fcol[c], P.fwid[c], T, true, rf.v[c], false);
+            for (int c = 0; c < NF; c++) issue(P.fcol[c], P.fwid[c], T, true, rf.v[c], false);
+        }
+    };
+    auto decode_filters = [&]() {
+        if constexpr (FW) {
+            const uint32_t wd[kPackedRows] = {rf.v[0].x, rf.v[0].y, rf.v[0].z, rf.v[0].w};
+#pragma unroll
+            for (int c = 0; c < NF; c++) {
+#pragma unroll
+                for (int k = 0; k < kPackedRows; k++) f.u[c][k] = __builtin_amdgcn_ubfe(wd[k], (uint32_t)P.fshift[c], (uint32_t)P.fbits[c]);
+            }
+        } else {
+#pragma unroll
+            for (int c = 0; c < NF; c++) packed_decode(P.fwid[c], rf.v[c], f.u[c]);
+        }
     };
     auto issue_rest = [&](const DynTile &T, bool wanted) {
         if (TIME) issue(P.tcol, P.twid, T, wanted, rt.v[0], false);
@@ -623,8 +646,7 @@ __device__ __forceinline__ void packed_scan_dyn(const FastPlan &P, int64_t *lds,
         // while the rows of t are consumed
         PackedTile<0> f0;
         auto filter_bits = [&](const DynTile &T) -> uint32_t {
-#pragma unroll
-            for (int c = 0; c < NF; c++) packed_decode(P.fwid[c], rf.v[c], f.u[c]);
+            decode_filters();
             const uint32_t left = lane_left(T);
             uint32_t bits = 0;
 #pragma unroll
@@ -669,8 +691,7 @@ __device__ __forceinline__ void packed_scan_dyn(const FastPlan &P, int64_t *lds,
     issue_rest(T0, true);
     cur.draw_ahead();
     while (T0.rows) {
-#pragma unroll
-        for (int c = 0; c < NF; c++) packed_decode(P.fwid[c], rf.v[c], f.u[c]);
+        decode_filters();
         decode_rest();
         const DynTile T1 = cur.next();  // (every load issued so far has been waited for)
         issue_filters(T1);
@@ -687,10 +708,12 @@ __device__ __forceinline__ void packed_scan_dyn(const FastPlan &P, int64_t *lds,
 // launcher picks the instantiation, and a lean kernel holds the lean body only.  (Two bodies chosen per tile inside one loop
 // cost the loop 20 more spilled scalar registers; DESIGN 3.6 has the same finding for two loops in one kernel.)
 // DYN: FastPlan::dyn, likewise a property of the kernel -- the dynamic loops instead of the static ones (packed_scan_dyn).
-template <int NF, int NG, int NA, int MODE, bool TIME, bool G1, bool NUL, int RING = 0, int LEANV = 0, bool DYN = false>
+// FW: the dynamic loops read a filter word in the filter columns' place (packed_scan_dyn).
+template <int NF, int NG, int NA, int MODE, bool TIME, bool G1, bool NUL, int RING = 0, int LEANV = 0, bool DYN = false, bool FW = false>
 __global__ __launch_bounds__(kWgThreads, SYBL_PACKED_WAVES_PER_EU) void k_scan_packed(const FastPlan P) {
     static_assert(LEANV == 0 || !NUL, "the NUL kernels mix row bodies: no proofs");
     static_assert(!DYN || (!NUL && RING == 0), "dynamic dealing is the plain kernels'");
+    static_assert(!FW || (DYN && NF >= kFwordMinFields), "filter words are the dynamic loops', for two filter columns and more");
     static_assert(!(LEANV & kLeanMoments) || (MODE == kFastMoments && NA >= 1), "the lean layout is moments mode's");
     static_assert(!(LEANV & kLeanProved) || MODE == kFastMoments || MODE == kFastHist, "the proved bodies are the bucket modes'");
     extern __shared__ int64_t lds[];
@@ -702,7 +725,7 @@ __global__ __launch_bounds__(kWgThreads, SYBL_PACKED_WAVES_PER_EU) void k_scan_p
 
     uint32_t matched = 0, overflow = 0;
     const uint64_t clock_in = P.wg_clock ? wall_clock64() : 0;  // (SYBL_WG_CLOCKS=1: when this workgroup's loop began and ended)
-    if constexpr (DYN) packed_scan_dyn<NF, NG, NA, MODE, TIME, G1, LEANV>(P, lds, L, kMax32 && !P.ext_general, matched, overflow);
+    if constexpr (DYN) packed_scan_dyn<NF, NG, NA, MODE, TIME, G1, LEANV, FW>(P, lds, L, kMax32 && !P.ext_general, matched, overflow);
     // (DYN: no segments -- the static loops below compile to nothing)
     const int s0 = DYN ? 0 : P.wg_seg_begin[blockIdx.x], s1 = DYN ? 0 : P.wg_seg_begin[blockIdx.x + 1];
     for (int si = s0; si < s1; si++) {
@@ -1352,6 +1375,28 @@ static hipError_t emit_packed_launch_nf(const EmitPlan &E, int ng, int na, int n
 #undef SYBL_EMITP_CASE
 }
 
+// the dynamic kernels (FastPlan::dyn) of one shape: the instantiation for the plan's lean bits, reading the filter columns or,
+// FW, a filter word
+template <int NF, int NG, int NA, int MODE, bool TIME, bool G1, bool FW, class LAUNCH>
+static hipError_t packed_launch_dyn(const FastPlan &P, LAUNCH &&launch_lean) {
+    if constexpr (NA >= 1 && MODE == kFastMoments) {
+        switch (P.lean) {
+        case 0: return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, false, 0, 0, true, FW>);
+        case kLeanMoments: return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, false, 0, kLeanMoments, true, FW>);
+        case kLeanProved: return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, false, 0, kLeanProved, true, FW>);
+        case kLeanMoments | kLeanProved: return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, false, 0, kLeanMoments | kLeanProved, true, FW>);
+        default: return hipErrorInvalidValue;
+        }
+    } else if constexpr (NA >= 1 && MODE == kFastHist) {
+        if (P.lean == kLeanProved) return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, false, 0, kLeanProved, true, FW>);
+        if (P.lean) return hipErrorInvalidValue;
+        return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, false, 0, 0, true, FW>);
+    } else {
+        if (P.lean) return hipErrorInvalidValue;
+        return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, false, 0, 0, true, FW>);
+    }
+}
+
 template <int NF, int NG, int NA, int MODE, bool TIME, bool G1, bool NUL>
 static hipError_t packed_launch_k1(const FastPlan &P, int n_wg, size_t lds_bytes, hipStream_t st) {
     // SYBL_PACKED_RING=1..3 (tuning): the BASELINE shapes with an explicit ring depth, for same-box A/B runs
@@ -1369,26 +1414,22 @@ static hipError_t packed_launch_k1(const FastPlan &P, int n_wg, size_t lds_bytes
     if (P.dyn) {
         if constexpr (!NUL) {
             if (!P.pieces || !P.piece_queue || P.n_pieces < 1 || P.piece_cap < 1) return hipErrorInvalidValue;
-            if constexpr (NA >= 1 && MODE == kFastMoments) {
-                switch (P.lean) {
-                case 0: return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, NUL, 0, 0, true>);
-                case kLeanMoments: return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, NUL, 0, kLeanMoments, true>);
-                case kLeanProved: return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, NUL, 0, kLeanProved, true>);
-                case kLeanMoments | kLeanProved: return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, NUL, 0, kLeanMoments | kLeanProved, true>);
-                default: return hipErrorInvalidValue;
+            // FastPlan::fword: the FW kernels (the planner takes a word for NF >= 2 only; the fields must lie inside the word)
+            if (P.fword) {
+                if constexpr (NF >= kFwordMinFields) {
+                    for (int c = 0; c < NF; c++)
+                        if (P.fbits[c] < 1 || P.fshift[c] < 0 || P.fshift[c] + P.fbits[c] > kFwordBits) return hipErrorInvalidValue;
+                    return packed_launch_dyn<NF, NG, NA, MODE, TIME, G1, true>(P, launch_lean);
+                } else {
+                    return hipErrorInvalidValue;
                 }
-            } else if constexpr (NA >= 1 && MODE == kFastHist) {
-                if (P.lean == kLeanProved) return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, NUL, 0, kLeanProved, true>);
-                if (P.lean) return hipErrorInvalidValue;
-                return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, NUL, 0, 0, true>);
-            } else {
-                if (P.lean) return hipErrorInvalidValue;
-                return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, NUL, 0, 0, true>);
             }
+            return packed_launch_dyn<NF, NG, NA, MODE, TIME, G1, false>(P, launch_lean);
         } else {
             return hipErrorInvalidValue;
         }
     }
+    if (P.fword) return hipErrorInvalidValue;  // (a filter word is read by the dynamic loops alone)
     // FastPlan::lean: the kernel must be the one the planner sized the table for.  (The lean kernels have no ring variants:
     // SYBL_PACKED_RING acts on a plan without lean -- set SYBL_NO_LEAN=1 beside it.)
     if (P.lean) {

@@ -936,6 +936,150 @@ Column *column_build_narrow(Table *t, Column *c) {
     return r;
 }
 
+// ------------------------------------------------------------------ filter words (Table::fwords, fword.h)
+static std::string fword_list(const Table *t, const FilterWord &w, bool names) {
+    std::string s;
+    for (int i = 0; i < w.n; i++) s += (i ? "," : "") + (names ? t->cols[(size_t)w.cols[(size_t)i]]->name : std::to_string(w.bits[i]));
+    return s;
+}
+
+// SYBL_FWORD_MIN_ROWS (default 2^25 physical rows, the narrow twin's reasoning: below it a word saves a scan microseconds for a
+// pass over its columns and 4 B/row of HBM).  SYBL_NO_FWORD=1: no plan reads a word (the same-binary A/B switch).
+// SYBL_FWORD_MAX (default 2): the words a table holds; the least recently planned one goes first.
+// SYBL_PLAN_TRACE=1: `filter word: cols=c04,c05,c06 bits=10,10,10 rows=.. converted=.. bytes=..` when rows were converted,
+// `filter word: cols=.. freed` when a word goes.
+std::shared_ptr<FilterWord> table_build_fword(Table *t, const int *cols_in, int n) {
+    if (n < kFwordMinFields || n > kFwordMaxFields) return nullptr;
+    std::vector<int> cols(cols_in, cols_in + n);
+    std::sort(cols.begin(), cols.end());  // the key is the SET: the same filters in another order reuse the word
+    if (std::adjacent_find(cols.begin(), cols.end()) != cols.end() || cols.front() < 0 || cols.back() >= (int)t->cols.size()) return nullptr;
+    int64_t min_rows = (int64_t)1 << 25, max_words = 2;
+    if (const char *e = env("SYBL_FWORD_MIN_ROWS")) min_rows = std::max<int64_t>(atoll(e), 1);
+    if (const char *e = env("SYBL_FWORD_MAX")) max_words = std::max<int64_t>(atoll(e), 1);
+    const bool trace = env("SYBL_PLAN_TRACE") != nullptr;
+    auto held = [&]() { return std::find_if(t->fwords.begin(), t->fwords.end(), [&](const std::shared_ptr<FilterWord> &w) { return w->cols == cols; }); };
+    auto drop = [&](bool say) {  // the table's share goes; a prepared query that reads the word keeps its own
+        auto it = held();
+        if (it == t->fwords.end()) return;
+        if (say && trace) fprintf(stderr, "filter word: cols=%s freed\n", fword_list(t, **it, true).c_str());
+        t->fwords.erase(it);
+    };
+    auto it = held();
+    const bool current = it != t->fwords.end() && (*it)->version == t->version;
+    if (env("SYBL_NO_FWORD") || t->phys_rows < min_rows) {
+        // (a word of this version may be what another prepared query scans: it stays, this plan just does not read it)
+        if (it != t->fwords.end() && !current) drop(false);
+        return nullptr;
+    }
+    if (current) {
+        (*it)->planned = ++t->fword_clock;
+        return *it;
+    }
+    // eligibility from the EXACT extrema (declared bounds say nothing about the stored bits)
+    if (table_ensure_stats(t) != SYBL_OK) return nullptr;
+    uint32_t max_off[kFwordMaxFields];
+    int32_t bits[kFwordMaxFields], shift[kFwordMaxFields];
+    int widths = 0;
+    bool eligible = true;
+    for (int i = 0; i < n && eligible; i++) {
+        const Column *c = t->cols[(size_t)cols[(size_t)i]].get();
+        eligible = c->type == SYBL_INT_VAL && (c->elem == 1 || c->elem == 2 || c->elem == 4) && c->d_data && c->n_pop > 0 && c->exact_min >= c->vbase &&
+                   !c->has_missing && (unsigned __int128)((__int128)c->exact_max - (__int128)c->vbase) <= (unsigned __int128)UINT32_MAX;
+        if (!eligible) break;
+        max_off[i] = (uint32_t)((uint64_t)c->exact_max - (uint64_t)c->vbase);
+        widths += c->elem;
+    }
+    // (a word must save bytes: two 2-byte columns are as well read as they are)
+    eligible = eligible && fword_layout(max_off, n, bits, shift) <= kFwordBits && widths >= 5;
+    if (!eligible) {
+        drop(true);
+        return nullptr;
+    }
+    // What changed since the word was last checked, by column_build_narrow's rule: the versions differ by exactly the blocks
+    // added iff blocks were appended and nothing else happened -- the rows the word covers are then what they were, and only the
+    // rows beyond them are packed, into the RECORDED fields.  Another width or base of a column, or anything else: the word is
+    // built again from the first row.  Extrema that no longer fit the recorded fields: the word is freed and this plan reads the
+    // columns (while the columns still fit 32 bits in all, the next prepare builds a word with the fields they need now).
+    std::shared_ptr<FilterWord> w = it != t->fwords.end() ? *it : nullptr;
+    int64_t from = 0;
+    if (w) {
+        bool same = true, fits = true;
+        for (int i = 0; i < n; i++) {
+            const Column *c = t->cols[(size_t)cols[(size_t)i]].get();
+            same = same && w->elem[i] == c->elem && w->vbase[i] == c->vbase;
+            fits = fits && bits[i] <= w->bits[i];
+        }
+        if (same && fits && w->rows <= t->phys_rows && (int64_t)t->blocks.size() >= w->blocks && t->version - w->version == (int64_t)t->blocks.size() - w->blocks)
+            from = w->rows & ~(int64_t)3;  // (the quad the old last row shares with the first new one is written again)
+        if (from == 0) {
+            drop(same && !fits);
+            w.reset();
+            if (same && !fits) return nullptr;  // (this plan reads the columns; the next prepare finds no word and lays out a new one)
+        }
+    }
+    hipStream_t st = t->ctx->stream;
+    auto give_up = [&]() -> std::shared_ptr<FilterWord> {
+        (void)hipGetLastError();  // an allocation that failed is no error of the query: it plans on the columns
+        drop(false);
+        return nullptr;
+    };
+    if (load_sync_all(t->ctx) != SYBL_OK) return give_up();
+    const int64_t need = t->phys_rows + kTileRows;  // (+ a tile, like table_reserve: the scan's descriptors end on whole lanes)
+    if (!w || need > w->cap_rows) {
+        // a new array in a new word: a prepared query that still holds the old one keeps scanning the old array
+        auto nw = std::make_shared<FilterWord>();
+        nw->cols = cols;
+        nw->n = n;
+        for (int i = 0; i < n; i++) {
+            const Column *c = t->cols[(size_t)cols[(size_t)i]].get();
+            nw->bits[i] = w ? w->bits[i] : bits[i];
+            nw->shift[i] = w ? w->shift[i] : shift[i];
+            nw->elem[i] = c->elem;
+            nw->vbase[i] = c->vbase;
+        }
+        if (!w)
+            while ((int64_t)t->fwords.size() >= max_words) {  // bounded HBM: the least recently planned word makes room
+                auto lru = std::min_element(t->fwords.begin(), t->fwords.end(),
+                                            [](const std::shared_ptr<FilterWord> &a, const std::shared_ptr<FilterWord> &b) { return a->planned < b->planned; });
+                if (trace) fprintf(stderr, "filter word: cols=%s freed\n", fword_list(t, **lru, true).c_str());
+                t->fwords.erase(lru);
+            }
+        const int64_t cap = w ? std::max(need, w->cap_rows + w->cap_rows / 2) : need;
+        if (hipMalloc(&nw->d_data, (size_t)cap * 4) != hipSuccess) {
+            nw->d_data = nullptr;
+            return give_up();
+        }
+        nw->cap_rows = cap;
+        if (w && from > 0) {
+            if (hipMemcpyAsync(nw->d_data, w->d_data, (size_t)from * 4, hipMemcpyDeviceToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return give_up();
+        }
+        if (w) drop(false);
+        t->fwords.push_back(nw);
+        w = nw;
+    }
+    FwordPack S;
+    memset(&S, 0, sizeof(S));
+    S.n = n;
+    for (int i = 0; i < n; i++) {
+        const Column *c = t->cols[(size_t)cols[(size_t)i]].get();
+        S.col[i] = c->d_data;
+        S.wid[i] = c->elem;
+        S.shift[i] = w->shift[i];
+        S.bits[i] = w->bits[i];
+    }
+    hipError_t e = launch_pack_fword(S, w->d_data, from, t->phys_rows - from, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return give_up();
+    if (trace)
+        fprintf(stderr, "filter word: cols=%s bits=%s rows=%lld converted=%lld bytes=%lld\n", fword_list(t, *w, true).c_str(), fword_list(t, *w, false).c_str(),
+                (long long)t->phys_rows, (long long)(t->phys_rows - from), (long long)(w->cap_rows * 4));
+    w->rows = t->phys_rows;
+    w->version = t->version;
+    w->blocks = (int64_t)t->blocks.size();
+    w->planned = ++t->fword_clock;
+    return w;
+}
+
 int column_upload_set(Table *t, Column *c) {
     if (c->type != SYBL_SET_VAL || !c->set_dirty) return SYBL_OK;
     // offsets for every physical row + the scan's one-tile slack
@@ -1132,6 +1276,7 @@ int64_t sybl_table_hbm_bytes(const sybl_table *t) {
         if (c->carried_weight) b += c->carried_weight->cap_rows * c->carried_weight->elem;
         if (c->narrow) b += c->narrow->cap_rows * c->narrow->elem;  // ... a 4-byte column's narrow twin
     }
+    for (auto &w : t->fwords) b += w->cap_rows * 4;  // the filter words the table holds (one a query alone still holds is that query's)
     return b;
 }
 

@@ -7,6 +7,8 @@
 // and, at R = 4, the same mix with the two 4-byte columns stored at 3 bytes per row (14 B/row, k_loads_narrow): a dwordx4 at a
 // 12-byte lane stride behind a 768-byte descriptor (the fourth dword of lane 63 is range-checked away), or a dwordx3.  These
 // run in turns against the 16 B mix and print min / median / max, so the two ranges can be set side by side.
+// Last, the 14 B mix against two 12 B mixes (k_loads_fword), in turns again: the three 2-byte filter columns as one 4-byte
+// "filter word" column (five loads per tile), and that with the two 1-byte key columns as one 2-byte column besides (four).
 // build: hipcc --offload-arch=gfx950 -O3 -o loadpat loadpat.hip ; run: ./loadpat [rows]
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -84,6 +86,30 @@ __global__ __launch_bounds__(kThreads) void k_loads_narrow(Cols C, int64_t rows,
     if (acc == 0x12345678u) out[0] = acc;
 }
 
+// The 14 B mix (V = 0) against 12 B mixes: V = 1 reads one 4-byte column for the three 2-byte ones (a full dwordx4, 5 loads per
+// tile); V = 2 also reads one 2-byte column (a dwordx2) for the two 1-byte ones (4 loads per tile).  X holds those two columns.
+template <int V>
+__global__ __launch_bounds__(kThreads) void k_loads_fword(Cols C, Cols X, int64_t rows, uint32_t *out) {
+    const int64_t per_wg = (rows / gridDim.x) / (kThreads * 4) * (kThreads * 4);
+    const int64_t start = (int64_t)blockIdx.x * per_wg;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    uint32_t acc = 0;
+    for (int64_t t = 0; t < per_wg; t += kThreads * 4) {
+        const int64_t wave_row = start + t + (int64_t)wave * 256;
+        if (V == 0) {
+#pragma unroll
+            for (int c = 0; c < 3; c++) acc ^= load_lane<16>(C.c[c] + wave_row * 2, 512u, lane * 8);
+        } else acc ^= load_lane<16>(X.c[0] + wave_row * 4, 1024u, lane * 16);
+        if (V <= 1) {
+#pragma unroll
+            for (int c = 3; c < 5; c++) acc ^= load_lane<4>(C.c[c] + wave_row, 256u, lane * 4);
+        } else acc ^= load_lane<8>(X.c[1] + wave_row * 2, 512u, lane * 8);
+#pragma unroll
+        for (int c = 5; c < 7; c++) acc ^= load_lane<16>(C.c[c] + wave_row * 3, 768u, lane * 12);
+    }
+    if (acc == 0x12345678u) out[0] = acc;
+}
+
 int main(int argc, char **argv) {
     const int64_t rows = argc > 1 ? atoll(argv[1]) : 1000000000LL;
     Cols C;
@@ -94,6 +120,15 @@ int main(int argc, char **argv) {
         if (hipMalloc(&p, (size_t)rows * widths[c] + 4096) != hipSuccess) { printf("alloc failed\n"); return 1; }
         hipMemset(p, c + 1, (size_t)rows * widths[c] + 4096);
         C.c[c] = (const uint8_t *)p;
+    }
+    Cols X = {};
+    const int xwidths[2] = {4, 2};  // the filter word and the key pair of k_loads_fword
+    for (int c = 0; c < 2; c++) {
+        X.w[c] = xwidths[c];
+        void *p;
+        if (hipMalloc(&p, (size_t)rows * xwidths[c] + 4096) != hipSuccess) { printf("alloc failed\n"); return 1; }
+        hipMemset(p, c + 8, (size_t)rows * xwidths[c] + 4096);
+        X.c[c] = (const uint8_t *)p;
     }
     uint32_t *out;
     hipMalloc((void **)&out, 4);
@@ -140,6 +175,31 @@ int main(int argc, char **argv) {
                 for (int j = i + 1; j < kTurns - 1; j++)
                     if (m[j] < m[i]) { float t = m[i]; m[i] = m[j]; m[j] = t; }
             const double b = v == 0 ? 16.0 : 14.0;
+            printf("%-34s wgs %4d  min %.3f  med %.3f  max %.3f ms  %.0f GB/s of %.0f B/row at the median\n", names[v], wgs, m[0],
+                   m[(kTurns - 1) / 2], m[kTurns - 2], rows * b / (m[(kTurns - 1) / 2] * 1e-3) / 1e9, b);
+        }
+    }
+    // the 14 B mix against the 12 B mixes, in turns as above
+    for (int wgs : {256, 512}) {
+        const int kTurns = 11;
+        float ms[3][kTurns];
+        for (int it = 0; it < kTurns; it++)
+            for (int v = 0; v < 3; v++) {
+                hipEventRecord(e0);
+                if (v == 0) hipLaunchKernelGGL((k_loads_fword<0>), dim3(wgs), dim3(kThreads), 0, 0, C, X, rows, out);
+                if (v == 1) hipLaunchKernelGGL((k_loads_fword<1>), dim3(wgs), dim3(kThreads), 0, 0, C, X, rows, out);
+                if (v == 2) hipLaunchKernelGGL((k_loads_fword<2>), dim3(wgs), dim3(kThreads), 0, 0, C, X, rows, out);
+                hipEventRecord(e1);
+                hipEventSynchronize(e1);
+                hipEventElapsedTime(&ms[v][it], e0, e1);
+            }
+        const char *names[3] = {"14 B mix (3 x 2-byte filters)", "12 B mix (filter word)", "12 B mix (filter word, key pair)"};
+        for (int v = 0; v < 3; v++) {
+            float *m = ms[v] + 1;
+            for (int i = 0; i < kTurns - 1; i++)
+                for (int j = i + 1; j < kTurns - 1; j++)
+                    if (m[j] < m[i]) { float t = m[i]; m[i] = m[j]; m[j] = t; }
+            const double b = v == 0 ? 14.0 : 12.0;
             printf("%-34s wgs %4d  min %.3f  med %.3f  max %.3f ms  %.0f GB/s of %.0f B/row at the median\n", names[v], wgs, m[0],
                    m[(kTurns - 1) / 2], m[kTurns - 2], rows * b / (m[(kTurns - 1) / 2] * 1e-3) / 1e9, b);
         }
