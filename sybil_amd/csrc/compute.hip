@@ -3,13 +3,14 @@
 // are compute_expr.h, the arithmetic of every op is compute_ops.h (shared with the kernel).  This file is the device work and the
 // host code that drives it.
 //
-// The `t` half of the output IS sybl_table_concat of t alone (concat_run).  Expression k is evaluated on the OUTPUT's own columns
+// The `t` half of the output IS sybl_table_concat of t alone (derived_copy, derived.h; the call wrapper, the block search and
+// the statistics -- derived_block_stats -- are there too).  Expression k is evaluated on the OUTPUT's own columns
 // at each physical row -- no row of t has to be located again, and expression k may name computed columns 0 .. k-1.
 //
 //   k_cx_eval<false, 0>  the range pass: every live row evaluated; per lane the running min / max of the populated results and
 //                        their count, reduced over the wave (shuffles), then through LDS, and ONE signed 64-bit atomic min, one
-//                        max and one add per workgroup.  The host reads the three words back, fits (width, base) with concat's
-//                        rule, decides has_missing and the bitmap and reserves the column.
+//                        max and one add per workgroup.  The host reads the three words back, fits (width, base) with the storage
+//                        rule (colstats.h), decides has_missing and the bitmap and reserves the column.
 //   k_cx_eval<true, W>   the store pass: evaluates again and writes (v - base) at width W, 0 where unpopulated and in padding; a
 //                        lane writes whole dwords.  Where the column has a bitmap its words are OR-ed together from the 8 lanes
 //                        that hold a word's 32 rows.
@@ -26,11 +27,9 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <new>
 
 #include "compute_expr.h"
-#include "engine.h"
-#include "gather.h"
+#include "derived.h"
 
 namespace sybl {
 
@@ -38,12 +37,6 @@ constexpr int kCxThreads = 256;
 constexpr int kCxRows = 4;                          // per lane
 constexpr int kCxTileRows = kCxThreads * kCxRows;   // 1024
 constexpr int kCxWgPerCu = 8;
-
-struct CxBlk {
-    int64_t start;  // first physical row of a live block
-    int64_t n;      // its logical rows
-    int64_t tile0;  // tiles before it
-};
 
 struct CxCol {
     const void *data;       // nullptr: a set column, or no row was ever written
@@ -57,7 +50,7 @@ struct CxArgs {
     uint32_t ops[kCxMaxOps];  // op | arg << 8
     int64_t consts[kCxMaxOps];
     CxCol cols[kCxMaxCols];
-    const CxBlk *blk;
+    const RowBlk *blk;  // base: the tiles before a block
     int64_t n_tiles;
     int32_t n_ops, nb;
     void *out;             // store pass
@@ -209,14 +202,8 @@ __global__ __launch_bounds__(kCxThreads) void k_cx_eval(const CxArgs A) {
     const int tid = (int)threadIdx.x;
     long long mn = INT64_MAX, mx = INT64_MIN, cnt = 0;
     for (int64_t tile = blockIdx.x; tile < A.n_tiles; tile += gridDim.x) {
-        int lo = 0, hi = A.nb - 1;  // the last block whose tile0 <= tile: uniform, scalar
-        while (lo < hi) {
-            const int m = (lo + hi + 1) >> 1;
-            if (A.blk[m].tile0 <= tile) lo = m;
-            else hi = m - 1;
-        }
-        const CxBlk B = A.blk[lo];
-        const int64_t p0 = B.start + (tile - B.tile0) * kCxTileRows + (int64_t)tid * kCxRows;
+        const RowBlk B = A.blk[block_of(A.blk, A.nb, tile, &RowBlk::base)];  // (uniform, scalar)
+        const int64_t p0 = B.start + (tile - B.base) * kCxTileRows + (int64_t)tid * kCxRows;
         const int64_t pad_end = B.start + ((B.n + 31) & ~(int64_t)31);
         const bool active = p0 < pad_end;  // (8 lanes = one 32-row word: all of them active or none)
         const int64_t left = B.start + B.n - p0;
@@ -289,15 +276,10 @@ __global__ __launch_bounds__(kCxThreads) void k_cx_eval(const CxArgs A) {
 
 namespace {
 
-inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
-
 void launch_eval(bool store, int width, const CxArgs &A, unsigned grid, size_t lds, hipStream_t st) {
     const dim3 g(grid), b(kCxThreads);
     if (!store) hipLaunchKernelGGL((k_cx_eval<false, 0>), g, b, lds, st, A);
-    else if (width == 8) hipLaunchKernelGGL((k_cx_eval<true, 8>), g, b, lds, st, A);
-    else if (width == 4) hipLaunchKernelGGL((k_cx_eval<true, 4>), g, b, lds, st, A);
-    else if (width == 2) hipLaunchKernelGGL((k_cx_eval<true, 2>), g, b, lds, st, A);
-    else hipLaunchKernelGGL((k_cx_eval<true, 1>), g, b, lds, st, A);
+    else by_width(width, [&](auto W) { hipLaunchKernelGGL((k_cx_eval<true, decltype(W)::value>), g, b, lds, st, A); });
 }
 
 // compiles `expr` against a column list; on a refusal the message is "column '<name>': <why>"
@@ -340,15 +322,8 @@ int run(Table *t, const sybl_compute_desc *d, TableOwner &O) {
     if ((rc = load_sync_all(ctx))) return rc;
 
     // ---- the t half: concat of t alone
-    {
-        sybl_table *tt = static_cast<sybl_table *>(t);
-        sybl_concat_desc cd{};
-        cd.n_tables = 1;
-        cd.tables = &tt;
-        if ((rc = concat_run(&cd, &O.t))) return rc;
-    }
+    if ((rc = derived_copy(t, O))) return rc;
     Table *o = O.t;
-    o->concat_stats = sybl_concat_stats{};  // (this table was made by compute)
     if (o->cols.size() != nt) return fail(SYBL_E_STATE, "sybl_table_compute: the copy of the table holds %d columns, not %d", (int)o->cols.size(), (int)nt);
     sybl_compute_stats *S = &o->compute_stats;
     const int64_t N = o->logical_rows, nb_out = (int64_t)o->blocks.size(), phys_out = o->phys_rows;
@@ -364,7 +339,7 @@ int run(Table *t, const sybl_compute_desc *d, TableOwner &O) {
         n->name = d->exprs[k].name;
         n->type = SYBL_INT_VAL;
         n->elem = n->canon();
-        if (o->compact_mode) concat_fit(n.get(), false, 0, 0, &n->elem, &n->vbase);
+        if (o->compact_mode) fit_storage(n->canon(), false, 0, 0, &n->elem, &n->vbase);
         att[k] = n.get();
         o->col_ix[n->name] = (int)o->cols.size();
         o->cols.push_back(std::move(n));
@@ -373,20 +348,20 @@ int run(Table *t, const sybl_compute_desc *d, TableOwner &O) {
     if (nb_out > INT32_MAX) return fail(SYBL_E_INVAL, "sybl_table_compute: more blocks than a launch counts");
 
     // ---- tiles per block
-    std::vector<CxBlk> blk;
+    std::vector<RowBlk> blk;
     int64_t n_tiles = 0;
     for (const Segment &b : o->blocks) {
         if (b.n <= 0) continue;
-        blk.push_back(CxBlk{b.start, b.n, n_tiles});
+        blk.push_back(RowBlk{b.start, b.n, n_tiles});
         n_tiles += (round_up(b.n, 32) + kCxTileRows - 1) / kCxTileRows;
     }
     const int64_t n_out = round_up(phys_out, 32);
     GatherPool pool;
-    CxBlk *d_blk = nullptr;
+    RowBlk *d_blk = nullptr;
     long long *d_acc = nullptr;
     if ((rc = pool.alloc(&d_blk, blk.size(), "compute blocks"))) return rc;
     if ((rc = pool.alloc(&d_acc, 3 * ne + 1, "compute extrema"))) return rc;
-    if ((rc = host_to_device(ctx, d_blk, blk.data(), blk.size() * sizeof(CxBlk), "compute blocks"))) return rc;
+    if ((rc = host_to_device(ctx, d_blk, blk.data(), blk.size() * sizeof(RowBlk), "compute blocks"))) return rc;
     std::vector<long long> h_acc(3 * ne + 1, 0);
     for (size_t k = 0; k < ne; k++) h_acc[3 * k] = INT64_MAX, h_acc[3 * k + 1] = INT64_MIN;
     if ((rc = host_to_device(ctx, d_acc, h_acc.data(), h_acc.size() * sizeof(long long), "compute extrema"))) return rc;
@@ -426,7 +401,7 @@ int run(Table *t, const sybl_compute_desc *d, TableOwner &O) {
         const bool missing = populated < N;
         S->unpopulated += N - populated;
         S->range_bytes += src_bytes;
-        if (o->compact_mode) concat_fit(n, populated > 0, populated > 0 ? got[0] : 0, populated > 0 ? got[1] : 0, &n->elem, &n->vbase);
+        if (o->compact_mode) fit_storage(n->canon(), populated > 0, populated > 0 ? got[0] : 0, populated > 0 ? got[1] : 0, &n->elem, &n->vbase);
         n->has_missing = missing;
         if ((rc = table_reserve(o, n, phys_out))) return rc;
         if (missing && (rc = valid_reserve(o, n, phys_out))) return rc;
@@ -444,33 +419,8 @@ int run(Table *t, const sybl_compute_desc *d, TableOwner &O) {
 
     // ---- statistics
     if ((rc = pool.event(&ev[4 * ne], st))) return rc;
-    int64_t *d_stats = nullptr;
-    if ((rc = pool.alloc(&d_stats, ne * 3 * (size_t)nb_out, "compute statistics"))) return rc;
-    for (size_t k = 0; k < ne; k++) {
-        Column *n = att[k];
-        int64_t *out = d_stats + k * 3 * (size_t)nb_out;
-        hipError_t e = launch_block_minmax(n->d_data, n->elem, n->vbase, n->d_valid, o->d_blocks, (int)nb_out, out, out + nb_out, out + 2 * nb_out, st);
-        if (e != hipSuccess) return hip_fail(e, "k_block_minmax");
-    }
-    if ((rc = pool.event(&ev[4 * ne + 1], st))) return rc;
-    std::vector<int64_t> stats(ne * 3 * (size_t)nb_out);
-    SYBL_HIP(hipMemcpyAsync(stats.data(), d_stats, stats.size() * 8, hipMemcpyDeviceToHost, st));
-    SYBL_HIP(hipStreamSynchronize(st));  // the ONE wait for the statistics of every block of every computed column
-    for (size_t k = 0; k < ne; k++) {
-        Column *n = att[k];
-        const int64_t *h = stats.data() + k * 3 * (size_t)nb_out;
-        n->blk_min.assign(h, h + nb_out);
-        n->blk_max.assign(h + nb_out, h + 2 * nb_out);
-        n->blk_pop.assign(h + 2 * nb_out, h + 3 * nb_out);
-        for (int64_t b = 0; b < nb_out; b++) {
-            if (n->blk_pop[(size_t)b] > 0) {
-                n->exact_min = std::min(n->exact_min, n->blk_min[(size_t)b]);
-                n->exact_max = std::max(n->exact_max, n->blk_max[(size_t)b]);
-            }
-            n->n_pop += n->blk_pop[(size_t)b];
-        }
-        n->stats_blocks = nb_out;
-    }
+    // (the ONE wait for the statistics of every block of every computed column)
+    if ((rc = derived_block_stats(o, att, o->d_blocks, nb_out, pool, "compute statistics", &ev[4 * ne + 1]))) return rc;
     o->version++;
     float f = 0;
     for (size_t k = 0; k < ne; k++) {
@@ -487,24 +437,8 @@ int run(Table *t, const sybl_compute_desc *d, TableOwner &O) {
 }  // namespace
 
 int compute_run(Table *t, const sybl_compute_desc *d, sybl_table **out) {
-    Ctx *ctx = t->ctx;
-    SYBL_HIP(hipSetDevice(ctx->device));
-    TableOwner O;
-    int rc;
-    try {
-        rc = run(t, d, O);
-    } catch (const std::bad_alloc &) {
-        rc = fail(SYBL_E_NOMEM, "sybl_table_compute: out of host memory");
-    } catch (const std::exception &e) {
-        rc = fail(SYBL_E_INVAL, "sybl_table_compute: %s", e.what());
-    }
-    if (rc) {
-        (void)hipStreamSynchronize(ctx->stream);  // (nothing of this call is in flight when its buffers go)
-        return rc;
-    }
-    *out = O.t;
-    O.t = nullptr;
-    return SYBL_OK;
+    TableOwner O;  // (run makes the table: the copy of t)
+    return derived_call(t->ctx, "sybl_table_compute", O, out, [&] { return run(t, d, O); });
 }
 
 }  // namespace sybl

@@ -11,7 +11,7 @@
 //                      the value goes through the (source, column) id -> id table, and value - dbase is written at WD
 //                      bytes.  The NARROWER side moves 16 bytes per lane, the wider side WW / WN 16-byte accesses of one
 //                      contiguous span, lane after lane: no sub-dword access, no LDS, no atomics.  One launch per (source,
-//                      column) over its run list; a wave finds the run of its first row by bisection (as k_dg_keys does).
+//                      column) over its run list; a wave finds the run of its first row by bisection (block_of, derived.h).
 //   k_cc_valid         validity words: copied where the source column has a bitmap, ones for the logical rows where it has
 //                      none but the output does; the padding bits of a block's last word are zero either way.  A source
 //                      that lacks the column leaves the zeroed words alone.
@@ -20,13 +20,14 @@
 //
 // Set columns: validity as above; the CSR (Column::h_set_off / h_set_vals) is concatenated on the host, member ids through
 // the same id table -- a host pass per set column.
+//
+// The storage rule is fit_storage (colstats.h), as for appended blocks; the call wrapper and the statistics of the remapped
+// columns (derived_block_stats) are derived.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <new>
 
-#include "engine.h"
-#include "gather.h"
+#include "derived.h"
 
 namespace sybl {
 
@@ -60,16 +61,8 @@ __global__ __launch_bounds__(kCcThreads) void k_cc_transcode(const void *__restr
     constexpr int NS = R * WS / 16;     // 16-byte loads per lane
     constexpr int ND = R * WD / 16;     // 16-byte stores per lane
     const int64_t i = ((int64_t)blockIdx.x * kCcThreads + threadIdx.x) * R;
-    const int64_t first = i - (int64_t)(threadIdx.x & 63) * R;
-    if (first >= T) return;
-    int a = 0, b = nr - 1;  // the last run whose lbase <= first: the same addresses in every lane
-    while (a < b) {
-        const int m = (a + b + 1) >> 1;
-        if (runs[m].lbase <= first) a = m;
-        else b = m - 1;
-    }
     if (i >= T) return;
-    while (a + 1 < nr && runs[a + 1].lbase <= i) a++;
+    const int a = block_of(runs, nr, i - (int64_t)(threadIdx.x & 63) * R, i, &CcRun::lbase);
     const int64_t off = i - runs[a].lbase;
     const uint4 *sp = (const uint4 *)((const char *)src + (size_t)(runs[a].src + off) * WS);
     uint4 *dp = (uint4 *)((char *)dst + (size_t)(runs[a].dst + off) * WD);
@@ -118,17 +111,8 @@ __global__ __launch_bounds__(kCcThreads) void k_cc_transcode(const void *__restr
 __global__ __launch_bounds__(kCcThreads) void k_cc_valid(const uint32_t *__restrict__ valid, const CcBlk *__restrict__ blk, int nb, int64_t n_words,
                                                          uint32_t *__restrict__ out) {
     const int64_t i = (int64_t)blockIdx.x * kCcThreads + threadIdx.x;
-    const int64_t first = i - (threadIdx.x & 63);
-    if (first >= n_words) return;
-    int a = 0, b = nb - 1;
-    while (a < b) {
-        const int m = (a + b + 1) >> 1;
-        if (blk[m].wbase <= first) a = m;
-        else b = m - 1;
-    }
     if (i >= n_words) return;
-    while (a + 1 < nb && blk[a + 1].wbase <= i) a++;
-    const CcBlk B = blk[a];
+    const CcBlk B = blk[block_of(blk, nb, i - (threadIdx.x & 63), i, &CcBlk::wbase)];
     const int64_t w = i - B.wbase;
     uint32_t bits = valid ? valid[(B.src >> 5) + w] : 0xFFFFFFFFu;
     const int64_t left = B.n - w * 32;  // >= 1: the block has ceil(n / 32) words
@@ -136,26 +120,7 @@ __global__ __launch_bounds__(kCcThreads) void k_cc_valid(const uint32_t *__restr
     out[(B.dst >> 5) + w] = bits;
 }
 
-// (gather.h; shared with lookup.hip) table.cpp's fit_storage: the narrowest (width, base) that holds [lo, hi]; canonical storage when nothing narrower does
-void concat_fit(const Column *c, bool any, int64_t lo, int64_t hi, int *width, int64_t *base) {
-    *width = c->canon();
-    *base = 0;
-    if (!any) {
-        *width = 1;
-        return;
-    }
-    const unsigned __int128 range = (unsigned __int128)((__int128)hi - (__int128)lo);
-    const int f = range < 256 ? 1 : range < 65536 ? 2 : range < ((unsigned __int128)1 << 32) ? 4 : 8;
-    if (f < *width) {
-        *width = f;
-        *base = lo;
-    }
-}
-
 namespace {
-
-inline unsigned grid_for(int64_t n, int threads) { return (unsigned)std::max<int64_t>(1, (n + threads - 1) / threads); }
-inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 struct CcPiece {
     const void *src;
@@ -210,8 +175,6 @@ struct Source {
     CcRun *d_runs = nullptr;
     CcBlk *d_blks = nullptr;
 };
-
-const char *type_name(int ty) { return ty == SYBL_INT_VAL ? "int" : ty == SYBL_STR_VAL ? "str" : "set"; }
 
 int run(const sybl_concat_desc *d, Table *o, sybl_concat_stats *S) {
     Table *t0 = d->tables[0];
@@ -353,7 +316,7 @@ int run(const sybl_concat_desc *d, Table *o, sybl_concat_stats *S) {
             hi = std::max(hi, b);
             pop += c->n_pop;
         }
-        if (compact) concat_fit(n, any, lo, hi, &n->elem, &n->vbase);
+        if (compact) fit_storage(n->canon(), any, lo, hi, &n->elem, &n->vbase);
         n->exact_min = lo;
         n->exact_max = hi;
         n->n_pop = pop;
@@ -457,64 +420,39 @@ int run(const sybl_concat_desc *d, Table *o, sybl_concat_stats *S) {
     }
     if ((rc = pool.event(&ev[1], st))) return rc;
 
-    // ---- block statistics: the sources' own; recomputed where ids were remapped
-    int64_t n_re = 0;
-    for (size_t k = 0; k < nc; k++) n_re += recompute[k];
-    Segment *d_osegs = nullptr;
-    int64_t *d_stats = nullptr;
-    std::vector<int64_t> stats;
-    if (n_re) {
-        if ((rc = pool.alloc(&d_osegs, (size_t)nb_out, "concat blocks"))) return rc;
-        if ((rc = pool.alloc(&d_stats, (size_t)n_re * 3 * (size_t)nb_out, "concat statistics"))) return rc;
-        if ((rc = host_to_device(ctx, d_osegs, osegs.data(), osegs.size() * sizeof(Segment), "concat blocks"))) return rc;
-        int64_t j = 0;
-        for (size_t k = 0; k < nc; k++) {
-            if (!recompute[k]) continue;
-            const Column *n = o->cols[k].get();
-            int64_t *out = d_stats + j++ * 3 * nb_out;
-            hipError_t e = launch_block_minmax(n->d_data, n->elem, n->vbase, n->d_valid, d_osegs, (int)nb_out, out, out + nb_out, out + 2 * nb_out, st);
-            if (e != hipSuccess) return hip_fail(e, "k_block_minmax");
-        }
-        stats.resize((size_t)n_re * 3 * (size_t)nb_out);
-    }
-    if ((rc = pool.event(&ev[2], st))) return rc;
-    if (n_re) SYBL_HIP(hipMemcpyAsync(stats.data(), d_stats, stats.size() * 8, hipMemcpyDeviceToHost, st));
-    SYBL_HIP(hipStreamSynchronize(st));  // the ONE wait of the call
-
-    int64_t j_re = 0;
+    // ---- block statistics: recomputed where ids were remapped (the extrema with them); else the sources' own
+    std::vector<Column *> remapped;
     for (size_t k = 0; k < nc; k++) {
         Column *n = o->cols[k].get();
-        if (n->type == SYBL_SET_VAL) continue;
+        if (!recompute[k]) continue;
+        n->exact_min = INT64_MAX;
+        n->exact_max = INT64_MIN;
+        n->n_pop = 0;
+        remapped.push_back(n);
+    }
+    Segment *d_osegs = nullptr;
+    if (!remapped.empty()) {
+        if ((rc = pool.alloc(&d_osegs, (size_t)nb_out, "concat blocks"))) return rc;
+        if ((rc = host_to_device(ctx, d_osegs, osegs.data(), osegs.size() * sizeof(Segment), "concat blocks"))) return rc;
+    }
+    if ((rc = derived_block_stats(o, remapped, d_osegs, nb_out, pool, "concat statistics", &ev[2]))) return rc;  // the ONE wait of the call
+
+    for (size_t k = 0; k < nc; k++) {
+        Column *n = o->cols[k].get();
+        if (n->type == SYBL_SET_VAL || recompute[k]) continue;
         n->blk_min.assign((size_t)nb_out, INT64_MAX);
         n->blk_max.assign((size_t)nb_out, INT64_MIN);
         n->blk_pop.assign((size_t)nb_out, 0);
-        if (recompute[k]) {
-            const int64_t *h = stats.data() + j_re++ * 3 * nb_out;
-            n->exact_min = INT64_MAX;
-            n->exact_max = INT64_MIN;
-            n->n_pop = 0;
-            for (int64_t b = 0; b < nb_out; b++) {
-                n->blk_min[(size_t)b] = h[b];
-                n->blk_max[(size_t)b] = h[nb_out + b];
-                n->blk_pop[(size_t)b] = h[2 * nb_out + b];
-                if (h[2 * nb_out + b] > 0) {
-                    n->exact_min = std::min(n->exact_min, h[b]);
-                    n->exact_max = std::max(n->exact_max, h[nb_out + b]);
-                }
-                n->n_pop += h[2 * nb_out + b];
-            }
-        } else {
-            for (int s = 0; s < ns; s++) {
-                const Source &Z = src[(size_t)s];
-                const Column *c = sc[k][(size_t)s];
-                if (!c || !c->d_data) continue;
-                for (size_t b = 0; b < Z.blk_ix.size(); b++) {
-                    const size_t from = (size_t)Z.blk_ix[b], to = (size_t)Z.first_out + b;
-                    if (from >= c->blk_pop.size()) return fail(SYBL_E_STATE, "sybl_table_concat: column '%s' of table %d lacks its block statistics", n->name.c_str(), s);
-                    n->blk_min[to] = c->blk_min[from];
-                    n->blk_max[to] = c->blk_max[from];
-                    n->blk_pop[to] = c->blk_pop[from];
-                }
+        for (int s = 0; s < ns; s++) {
+            const Source &Z = src[(size_t)s];
+            const Column *c = sc[k][(size_t)s];
+            if (!c || !c->d_data) continue;
+            for (size_t b = 0; b < Z.blk_ix.size(); b++) {
+                const size_t from = (size_t)Z.blk_ix[b], to = (size_t)Z.first_out + b;
+                if (from >= c->blk_pop.size()) return fail(SYBL_E_STATE, "sybl_table_concat: column '%s' of table %d lacks its block statistics", n->name.c_str(), s);
+                n->blk_min[to] = c->blk_min[from];
+                n->blk_max[to] = c->blk_max[from];
+                n->blk_pop[to] = c->blk_pop[from];
             }
         }
         n->stats_blocks = nb_out;
@@ -566,27 +504,10 @@ int run(const sybl_concat_desc *d, Table *o, sybl_concat_stats *S) {
 
 int concat_run(const sybl_concat_desc *d, sybl_table **out) {
     Ctx *ctx = d->tables[0]->ctx;
-    SYBL_HIP(hipSetDevice(ctx->device));
     TableOwner O;
-    O.t = new (std::nothrow) sybl_table();
-    if (!O.t) return fail(SYBL_E_NOMEM, "sybl_table_concat: out of host memory");
-    O.t->ctx = ctx;
-    O.t->name = d->tables[0]->name;
-    int rc;
-    try {
-        rc = run(d, O.t, &O.t->concat_stats);
-    } catch (const std::bad_alloc &) {
-        rc = fail(SYBL_E_NOMEM, "sybl_table_concat: out of host memory");
-    } catch (const std::exception &e) {
-        rc = fail(SYBL_E_INVAL, "sybl_table_concat: %s", e.what());
-    }
-    if (rc) {
-        (void)hipStreamSynchronize(ctx->stream);  // (nothing of this call is in flight when its buffers go)
-        return rc;
-    }
-    *out = O.t;
-    O.t = nullptr;
-    return SYBL_OK;
+    int rc = derived_new_table(ctx, d->tables[0]->name, "sybl_table_concat", O);
+    if (rc) return rc;
+    return derived_call(ctx, "sybl_table_concat", O, out, [&] { return run(d, O.t, &O.t->concat_stats); });
 }
 
 }  // namespace sybl

@@ -21,24 +21,18 @@
 // gathered on the host from the permutation.
 //
 // Everything behind the sort -- layout, gather, validity, statistics, set columns, the block writer -- is gather_rows
-// (gather.h): select.hip runs it over its ascending row list and a column subset.
+// (derived.h): select.hip runs it over its ascending row list and a column subset.  The call wrapper, the block search and the
+// small helpers are derived.h too; the set-column gather is colstats.h.
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
-#include <new>
 
-#include "engine.h"
-#include "gather.h"
+#include "derived.h"
 
 namespace sybl {
 
 constexpr int kDgThreads = 256;
-
-struct DgBlock {
-    int64_t start;  // first physical row of a live source block
-    int64_t lbase;  // index of its first row among the live rows
-};
 
 // where output physical row p comes from: block j = p / stride holds sorted rows [j * block_rows, ...); rows of the padding
 // behind a block, and behind the last row, have no source
@@ -48,26 +42,18 @@ __device__ __forceinline__ bool dg_sorted_index(int64_t p, int64_t stride, int64
     return r < block_rows && *i < N;
 }
 
-// ---- keys.  A lane per live row; the wave finds the block of its first row by bisection (the same addresses in every lane:
-// broadcast loads) and every lane walks on from there.
+// ---- keys.  A lane per live row; blk: the live source blocks, base = the index of a block's first row among the live rows
+// (block_of, derived.h).
 template <int W, bool K64>
 __global__ __launch_bounds__(kDgThreads) void k_dg_keys(const void *__restrict__ col, int64_t vbase, const uint32_t *__restrict__ valid,
-                                                        const DgBlock *__restrict__ blk, int nb, int64_t N, int64_t lo,
+                                                        const RowBlk *__restrict__ blk, int nb, int64_t N, int64_t lo,
                                                         void *__restrict__ keys, uint32_t *__restrict__ rows) {
     const int64_t i = (int64_t)blockIdx.x * kDgThreads + threadIdx.x;
-    const int64_t first = i - (threadIdx.x & 63);
-    if (first >= N) return;
-    int a = 0, b = nb - 1;  // the last block whose lbase <= first
-    while (a < b) {
-        const int m = (a + b + 1) >> 1;
-        if (blk[m].lbase <= first) a = m;
-        else b = m - 1;
-    }
     if (i >= N) return;
-    while (a + 1 < nb && blk[a + 1].lbase <= i) a++;
-    const int64_t row = blk[a].start + (i - blk[a].lbase);
+    const int a = block_of(blk, nb, i - (threadIdx.x & 63), i, &RowBlk::base);
+    const int64_t row = blk[a].start + (i - blk[a].base);
     int64_t v = 0;
-    if (col != nullptr && (valid == nullptr || ((valid[row >> 5] >> (row & 31)) & 1u))) {
+    if (col != nullptr && (valid == nullptr || valid_bit(valid, row))) {
         if (W == 8) v = ((const int64_t *)col)[row];
         else if (W == 4) v = vbase + (int64_t)((const uint32_t *)col)[row];
         else if (W == 2) v = vbase + (int64_t)((const uint16_t *)col)[row];
@@ -111,7 +97,7 @@ __global__ __launch_bounds__(kDgThreads) void k_dg_valid(const uint32_t *__restr
     bool bit = false;
     if (dg_sorted_index(p, stride, block_rows, N, &i)) {
         const uint32_t s = perm[i];
-        bit = (valid[s >> 5] >> (s & 31)) & 1u;
+        bit = valid_bit(valid, s);
     }
     const unsigned long long m = __ballot(bit);
     const int lane = threadIdx.x & 63;
@@ -121,11 +107,8 @@ __global__ __launch_bounds__(kDgThreads) void k_dg_valid(const uint32_t *__restr
 
 namespace {
 
-inline unsigned grid_for(int64_t n, int threads) { return (unsigned)std::max<int64_t>(1, (n + threads - 1) / threads); }
-inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
-
 template <int W>
-void launch_keys(bool k64, const Column *c, const DgBlock *blk, int nb, int64_t N, int64_t lo, void *keys, uint32_t *rows, hipStream_t st) {
+void launch_keys(bool k64, const Column *c, const RowBlk *blk, int nb, int64_t N, int64_t lo, void *keys, uint32_t *rows, hipStream_t st) {
     if (k64)
         hipLaunchKernelGGL((k_dg_keys<W, true>), dim3(grid_for(N, kDgThreads)), dim3(kDgThreads), 0, st, (const void *)c->d_data, c->vbase,
                            (const uint32_t *)c->d_valid, blk, nb, N, lo, keys, rows);
@@ -144,7 +127,7 @@ void launch_gather(const void *src, const uint32_t *perm, int64_t N, int64_t blo
 
 }  // namespace
 
-// (gather.h) name, type, IntInfo, dictionaries, declared bounds, storage
+// (derived.h) name, type, IntInfo, dictionaries, declared bounds, storage
 void gather_make_columns(const Table *t, const std::vector<Column *> &src, Table *o) {
     o->compact_mode = t->compact_mode;
     for (const Column *c : src) {
@@ -167,7 +150,7 @@ void gather_make_columns(const Table *t, const std::vector<Column *> &src, Table
     }
 }
 
-// (gather.h) the back half of a digest, shared with select.hip: there the row list is ascending, here it is the sort's
+// (derived.h) the back half of a digest, shared with select.hip: there the row list is ascending, here it is the sort's
 // permutation -- the name it keeps below
 int gather_rows(Table *t, const std::vector<Column *> &src, const uint32_t *perm, int64_t N, int64_t block_rows, Table *o, GatherPool &pool,
                 const char *who, hipEvent_t *gathered, int64_t *bytes, int64_t *blocks) {
@@ -211,12 +194,7 @@ int gather_rows(Table *t, const std::vector<Column *> &src, const uint32_t *perm
         if (!c->d_data) {
             SYBL_HIP(hipMemsetAsync(n->d_data, 0, (size_t)n_out * (size_t)n->elem, st));
         } else {
-            switch (c->elem) {
-            case 8: launch_gather<8>(c->d_data, perm, N, block_rows, stride, n_out, n->d_data, st); break;
-            case 4: launch_gather<4>(c->d_data, perm, N, block_rows, stride, n_out, n->d_data, st); break;
-            case 2: launch_gather<2>(c->d_data, perm, N, block_rows, stride, n_out, n->d_data, st); break;
-            default: launch_gather<1>(c->d_data, perm, N, block_rows, stride, n_out, n->d_data, st); break;
-            }
+            by_width(c->elem, [&](auto W) { launch_gather<decltype(W)::value>(c->d_data, perm, N, block_rows, stride, n_out, n->d_data, st); });
             *bytes += N * 4 + 2 * N * (int64_t)c->elem;
         }
         SYBL_HIP(hipGetLastError());
@@ -240,24 +218,15 @@ int gather_rows(Table *t, const std::vector<Column *> &src, const uint32_t *perm
     if (any_set) {
         std::vector<uint32_t> hperm((size_t)N);
         SYBL_HIP(hipMemcpy(hperm.data(), perm, (size_t)N * 4, hipMemcpyDeviceToHost));
+        // the source row of every output physical row (padding rows: none; the table ends with its last row)
+        std::vector<uint32_t> map((size_t)phys_out, kSetNoRow);
+        for (int64_t i = 0; i < N; i++) map[(size_t)(i / block_rows * stride + i % block_rows)] = hperm[(size_t)i];
         for (size_t k = 0; k < nc; k++) {
             const Column *c = src[k];
             Column *n = o->cols[k].get();
             if (c->type != SYBL_SET_VAL) continue;
             n->h_set_off.assign(1, 0);
-            n->h_set_off.reserve((size_t)phys_out + 1);
-            for (int64_t j = 0; j < nb_out; j++) {
-                const int64_t rows = j + 1 < nb_out ? stride : last_n;  // (padding rows: empty sets; the table ends with its last row)
-                for (int64_t r = 0; r < rows; r++) {
-                    const int64_t i = j * block_rows + r;
-                    if (r < block_rows && i < N) {
-                        const size_t s = hperm[(size_t)i];
-                        if (s + 1 < c->h_set_off.size())
-                            n->h_set_vals.insert(n->h_set_vals.end(), c->h_set_vals.begin() + c->h_set_off[s], c->h_set_vals.begin() + c->h_set_off[s + 1]);
-                    }
-                    n->h_set_off.push_back((int64_t)n->h_set_vals.size());
-                }
-            }
+            set_gather(c->h_set_off, c->h_set_vals, map.data(), phys_out, n->h_set_off, n->h_set_vals);
             n->set_dirty = true;
         }
     }
@@ -321,11 +290,11 @@ int run(Table *t, Column *tc, int64_t block_rows, Table *o, sybl_digest_stats *S
     gather_make_columns(t, src, o);
 
     // ---- the source rows: the live blocks in resident order
-    std::vector<DgBlock> live;
+    std::vector<RowBlk> live;
     int64_t N = 0;
     for (const Segment &b : t->blocks) {
         if (b.n <= 0) continue;  // (a dead block, sybl_table_refresh)
-        live.push_back(DgBlock{b.start, N});
+        live.push_back(RowBlk{b.start, b.n, N});
         N += b.n;
     }
     if (N >= ((int64_t)1 << 31)) return fail(SYBL_E_INVAL, "digest: %lld rows are more than the sort orders (2^31 - 1)", (long long)N);
@@ -352,7 +321,7 @@ int run(Table *t, Column *tc, int64_t block_rows, Table *o, sybl_digest_stats *S
     }
     S->key_bits = bits;
     const size_t ksz = k64 ? 8 : 4;
-    DgBlock *d_blk = nullptr;
+    RowBlk *d_blk = nullptr;
     char *key0 = nullptr, *key1 = nullptr;
     uint32_t *row0 = nullptr, *perm = nullptr;
     if ((rc = pool.alloc(&d_blk, (size_t)nb_src, "digest blocks"))) return rc;
@@ -365,14 +334,9 @@ int run(Table *t, Column *tc, int64_t block_rows, Table *o, sybl_digest_stats *S
     else SYBL_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, (uint32_t *)key0, (uint32_t *)key1, row0, perm, (int)N, 0, bits, st));
     char *tmp = nullptr;
     if ((rc = pool.alloc(&tmp, tmp_bytes, "digest sort"))) return rc;
-    if ((rc = host_to_device(ctx, d_blk, live.data(), live.size() * sizeof(DgBlock), "digest blocks"))) return rc;
+    if ((rc = host_to_device(ctx, d_blk, live.data(), live.size() * sizeof(RowBlk), "digest blocks"))) return rc;
     if ((rc = pool.event(&ev[0], st))) return rc;
-    switch (tc->d_data ? tc->elem : 8) {
-    case 8: launch_keys<8>(k64, tc, d_blk, nb_src, N, lo, key0, row0, st); break;
-    case 4: launch_keys<4>(k64, tc, d_blk, nb_src, N, lo, key0, row0, st); break;
-    case 2: launch_keys<2>(k64, tc, d_blk, nb_src, N, lo, key0, row0, st); break;
-    default: launch_keys<1>(k64, tc, d_blk, nb_src, N, lo, key0, row0, st); break;
-    }
+    by_width(tc->d_data ? tc->elem : 8, [&](auto W) { launch_keys<decltype(W)::value>(k64, tc, d_blk, nb_src, N, lo, key0, row0, st); });
     SYBL_HIP(hipGetLastError());
     if ((rc = pool.event(&ev[1], st))) return rc;
 
@@ -404,27 +368,10 @@ int digest_run(Table *t, const char *time_col, int32_t block_rows, sybl_table **
         return fail(SYBL_E_INVAL, "digest: time column '%s' is a %s column; rows are ordered by an int column", name, tc->type == SYBL_STR_VAL ? "str" : "set");
     if (block_rows < 0 || block_rows > SYBL_BLOCK_ROWS) return fail(SYBL_E_INVAL, "digest: block_rows %d is outside 0 .. %d", block_rows, SYBL_BLOCK_ROWS);
     const int64_t br = block_rows ? block_rows : SYBL_BLOCK_ROWS;
-    SYBL_HIP(hipSetDevice(t->ctx->device));
     TableOwner O;
-    O.t = new (std::nothrow) sybl_table();
-    if (!O.t) return fail(SYBL_E_NOMEM, "digest: out of host memory");
-    O.t->ctx = t->ctx;
-    O.t->name = t->name;
-    int rc;
-    try {
-        rc = run(t, tc, br, O.t, &O.t->digest_stats);
-    } catch (const std::bad_alloc &) {
-        rc = fail(SYBL_E_NOMEM, "digest: out of host memory");
-    } catch (const std::exception &e) {
-        rc = fail(SYBL_E_INVAL, "digest: %s", e.what());
-    }
-    if (rc) {
-        (void)hipStreamSynchronize(t->ctx->stream);  // (nothing of this call is in flight when its buffers go)
-        return rc;
-    }
-    *out = O.t;
-    O.t = nullptr;
-    return SYBL_OK;
+    int rc = derived_new_table(t->ctx, t->name, "digest", O);
+    if (rc) return rc;
+    return derived_call(t->ctx, "digest", O, out, [&] { return run(t, tc, br, O.t, &O.t->digest_stats); });
 }
 
 }  // namespace sybl

@@ -2,11 +2,11 @@
 // broadcast form (every rank holds all of `dim`).  The semantics are restated in include/sybilgpu.h ("lookup") and DESIGN.md
 // 3.11; this file is the device work and the host code that drives it.
 //
-// The `t` half of the output IS sybl_table_concat of t alone (concat_run): rows, blocks, columns, storage, statistics.  The
+// The `t` half of the output IS sybl_table_concat of t alone (derived_copy, derived.h): rows, blocks, columns, storage, statistics.  The
 // attached columns are added to that table: output physical row p of a live block is the row the key column of the OUTPUT
 // holds at p, so the probe reads the output's own key column and no row of t has to be located again.
 //
-//   k_lk_build   a lane per live dim row (the wave bisects the block list for its first row, as k_dg_keys does): the key at its
+//   k_lk_build   a lane per live dim row (the wave bisects the block list for its first row: block_of, derived.h): the key at its
 //                stored width and base, the validity bit, the key's cell, an agent-scope atomicMin of the physical row number
 //                into first_row[cell] (all-ones = nobody yet).  The lowest row wins whatever the order of arrival.
 //                  direct  cell = v - lo over the key's tracked range
@@ -26,27 +26,20 @@
 //   k_lk_valid   validity words by ballot, as k_dg_valid: matched && (dim has no bitmap || dim bit).
 //   statistics   k_block_minmax (kernels.hip) over every attached column, one readback for all of them.
 //
-// Set columns: validity as above; the CSR is built on the host from the match list that was read back.
+// Set columns: validity as above; the CSR is built on the host from the match list that was read back (set_gather, colstats.h).
+// The call wrapper, the column list, the width dispatch and the statistics (BlockStats) are derived.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <new>
 
-#include "engine.h"
-#include "gather.h"
+#include "derived.h"
 #include "scan_generic.h"
 
 namespace sybl {
 
 constexpr int kLkThreads = 256;
-constexpr uint32_t kLkNone = 0xFFFFFFFFu;
+constexpr uint32_t kLkNone = kSetNoRow;  // all ones: no match
 enum { kLkDirect = 1, kLkHash = 2, kLkStr = 3 };
-
-struct LkBlk {
-    int64_t start;  // first physical row of a live block
-    int64_t n;      // its logical rows
-    int64_t lbase;  // index of its first row among the live rows
-};
 
 struct LkTable {
     uint32_t *first_row;  // [cells] (+ the side cell of the key -1 on the hash path)
@@ -64,8 +57,6 @@ __device__ __forceinline__ uint64_t lk_bits(const void *col, size_t row) {
     return ((const uint8_t *)col)[row];
 }
 
-__device__ __forceinline__ bool lk_bit(const uint32_t *valid, size_t row) { return (valid[row >> 5] >> (row & 31)) & 1u; }
-
 // sums `bit` over the workgroup; the total is in thread 0 (every thread of the workgroup calls this)
 __device__ __forceinline__ uint32_t lk_wg_count(bool bit, uint32_t *lds) {
     const unsigned long long m = __ballot(bit);
@@ -81,22 +72,15 @@ __device__ __forceinline__ uint32_t lk_wg_count(bool bit, uint32_t *lds) {
 // ---- build.  counters[0]: populated << 32 | occupied, counters[1]: keys that found no slot (hash)
 template <int W, int MODE>
 __global__ __launch_bounds__(kLkThreads) void k_lk_build(const void *__restrict__ col, int64_t vbase, const uint32_t *__restrict__ valid,
-                                                         const LkBlk *__restrict__ blk, int nb, int64_t R, LkTable T,
+                                                         const RowBlk *__restrict__ blk, int nb, int64_t R, LkTable T,
                                                          unsigned long long *__restrict__ counters) {
     __shared__ uint32_t lds[kLkThreads / 64];
     const int64_t i = (int64_t)blockIdx.x * kLkThreads + threadIdx.x;
     bool populated = false, first_here = false;
     if (i < R) {
-        const int64_t first = i - (threadIdx.x & 63);
-        int a = 0, b = nb - 1;  // the last block whose lbase <= first
-        while (a < b) {
-            const int m = (a + b + 1) >> 1;
-            if (blk[m].lbase <= first) a = m;
-            else b = m - 1;
-        }
-        while (a + 1 < nb && blk[a + 1].lbase <= i) a++;
-        const int64_t row = blk[a].start + (i - blk[a].lbase);
-        if (valid == nullptr || lk_bit(valid, (size_t)row)) {
+        const int a = block_of(blk, nb, i - (threadIdx.x & 63), i, &RowBlk::base);
+        const int64_t row = blk[a].start + (i - blk[a].base);
+        if (valid == nullptr || valid_bit(valid, (size_t)row)) {
             populated = true;
             const uint64_t v = (uint64_t)vbase + lk_bits<W>(col, (size_t)row);
             int64_t cell = -1;
@@ -142,23 +126,16 @@ __global__ __launch_bounds__(kLkThreads) void k_lk_build(const void *__restrict_
 // output's physical rows rounded up to 32.  counters[2]: matched.
 template <int W, int MODE>
 __global__ __launch_bounds__(kLkThreads) void k_lk_probe(const void *__restrict__ col, int64_t vbase, const uint32_t *__restrict__ valid,
-                                                         const LkBlk *__restrict__ blk, int nb, int64_t n_out, LkTable T,
+                                                         const RowBlk *__restrict__ blk, int nb, int64_t n_out, LkTable T,
                                                          const int32_t *__restrict__ lut, int64_t n_lut, uint32_t *__restrict__ match,
                                                          unsigned long long *__restrict__ counters) {
     __shared__ uint32_t lds[kLkThreads / 64];
     const int64_t p = (int64_t)blockIdx.x * kLkThreads + threadIdx.x;
     uint32_t m = kLkNone;
     if (p < n_out) {
-        const int64_t first = p - (threadIdx.x & 63);
-        int a = 0, b = nb - 1;  // the last block whose start <= first
-        while (a < b) {
-            const int mid = (a + b + 1) >> 1;
-            if (blk[mid].start <= first) a = mid;
-            else b = mid - 1;
-        }
-        while (a + 1 < nb && blk[a + 1].start <= p) a++;
+        const int a = block_of(blk, nb, p - (threadIdx.x & 63), p, &RowBlk::start);
         const bool live = p < blk[a].start + blk[a].n;  // (else a padding row)
-        if (live && col != nullptr && (valid == nullptr || lk_bit(valid, (size_t)p))) {
+        if (live && col != nullptr && (valid == nullptr || valid_bit(valid, (size_t)p))) {
             const uint64_t v = (uint64_t)vbase + lk_bits<W>(col, (size_t)p);
             if (MODE == kLkHash) {
                 if (v == kHashEmpty) {
@@ -205,7 +182,7 @@ __global__ __launch_bounds__(kLkThreads) void k_lk_gather(const void *__restrict
 #pragma unroll
     for (int k = 0; k < K; k++) {
         const uint32_t m = match[p0 + k];
-        if (m == kLkNone || (svalid != nullptr && !lk_bit(svalid, (size_t)m))) continue;
+        if (m == kLkNone || (svalid != nullptr && !valid_bit(svalid, (size_t)m))) continue;
         const uint64_t o = (uint64_t)sbase + lk_bits<WS>(src, (size_t)m) - (uint64_t)dbase;
         if (WD == 8) wide = o;
         else if (WD == 4) word = (uint32_t)o;
@@ -223,7 +200,7 @@ __global__ __launch_bounds__(kLkThreads) void k_lk_valid(const uint32_t *__restr
     bool bit = false;
     if (p < n_out) {
         const uint32_t m = match[p];
-        bit = m != kLkNone && (svalid == nullptr || lk_bit(svalid, (size_t)m));
+        bit = m != kLkNone && (svalid == nullptr || valid_bit(svalid, (size_t)m));
     }
     const unsigned long long b = __ballot(bit);
     const int lane = threadIdx.x & 63;
@@ -232,14 +209,11 @@ __global__ __launch_bounds__(kLkThreads) void k_lk_valid(const uint32_t *__restr
 
 namespace {
 
-inline unsigned grid_for(int64_t n, int threads) { return (unsigned)std::max<int64_t>(1, (n + threads - 1) / threads); }
-inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
-
 struct KeySide {
     const void *col;
     int64_t vbase;
     const uint32_t *valid;
-    const LkBlk *blk;
+    const RowBlk *blk;
     int nb;
     int64_t rows;  // build: live rows; probe: n_out
 };
@@ -270,26 +244,6 @@ void launch_gather(const Column *c, const uint32_t *match, int64_t n_out, Column
                        (const uint32_t *)c->d_valid, match, n_out, n->d_data, n->vbase);
 }
 
-template <int WS>
-void launch_gather_to(const Column *c, const uint32_t *match, int64_t n_out, Column *n, hipStream_t st) {
-    switch (n->elem) {
-    case 8: launch_gather<WS, 8>(c, match, n_out, n, st); break;
-    case 4: launch_gather<WS, 4>(c, match, n_out, n, st); break;
-    case 2: launch_gather<WS, 2>(c, match, n_out, n, st); break;
-    default: launch_gather<WS, 1>(c, match, n_out, n, st); break;
-    }
-}
-
-#define LK_BY_WIDTH(width, call)  \
-    switch (width) {              \
-    case 8: call(8); break;       \
-    case 4: call(4); break;       \
-    case 2: call(2); break;       \
-    default: call(1); break;      \
-    }
-
-const char *type_name(int ty) { return ty == SYBL_INT_VAL ? "int" : ty == SYBL_STR_VAL ? "str" : "set"; }
-
 // SYBL_LOOKUP_SLOTS: a power of two in 2 .. kHashMaxSlots
 bool slots_ok(long long n) { return n >= 2 && n <= kHashMaxSlots && (n & (n - 1)) == 0; }
 
@@ -313,16 +267,7 @@ int run(Table *t, const sybl_lookup_desc *d, TableOwner &O) {
         return fail(SYBL_E_INVAL, "sybl_table_lookup: key column '%s' is a %s column and '%s' of the dim table a %s column", kname, type_name(tk->type),
                     dkname, type_name(dk->type));
     std::vector<Column *> src;
-    if (d->columns && d->n_columns > 0) {
-        for (int i = 0; i < d->n_columns; i++) {
-            Column *c = dim->find(d->columns[i]);
-            if (!c) return fail(SYBL_E_INVAL, "sybl_table_lookup: unknown column '%s' of the dim table", d->columns[i] ? d->columns[i] : "(null)");
-            if (std::find(src.begin(), src.end(), c) == src.end()) src.push_back(c);
-        }
-    } else {
-        for (auto &cp : dim->cols)
-            if (cp.get() != dk) src.push_back(cp.get());
-    }
+    if ((rc = resolve_columns(dim, d->columns, d->n_columns, "sybl_table_lookup", " of the dim table", dk, &src))) return rc;
     const std::string prefix = d->prefix ? d->prefix : "";
     std::vector<std::string> names;
     for (const Column *c : src) {
@@ -338,11 +283,11 @@ int run(Table *t, const sybl_lookup_desc *d, TableOwner &O) {
     if ((rc = table_ensure_stats(dim))) return rc;  // (the tracked extrema; no version moves)
 
     // ---- dim's live rows
-    std::vector<LkBlk> dblk;
+    std::vector<RowBlk> dblk;
     int64_t R = 0;
     for (const Segment &b : dim->blocks) {
         if (b.n <= 0) continue;  // (a dead block, sybl_table_refresh)
-        dblk.push_back(LkBlk{b.start, b.n, R});
+        dblk.push_back(RowBlk{b.start, b.n, R});
         R += b.n;
     }
     const bool any_keys = R > 0 && dk->n_pop > 0 && dk->d_data != nullptr;
@@ -394,15 +339,8 @@ int run(Table *t, const sybl_lookup_desc *d, TableOwner &O) {
     }
 
     // ---- the t half: concat of t alone
-    {
-        sybl_table *tt = static_cast<sybl_table *>(t);
-        sybl_concat_desc cd{};
-        cd.n_tables = 1;
-        cd.tables = &tt;
-        if ((rc = concat_run(&cd, &O.t))) return rc;
-    }
+    if ((rc = derived_copy(t, O))) return rc;
     Table *o = O.t;
-    o->concat_stats = sybl_concat_stats{};  // (this table was made by lookup)
     sybl_lookup_stats *S = &o->lookup_stats;
     const int64_t N = o->logical_rows, nb_out = (int64_t)o->blocks.size(), phys_out = o->phys_rows;
     const int64_t n_out = round_up(phys_out, 32);
@@ -411,7 +349,7 @@ int run(Table *t, const sybl_lookup_desc *d, TableOwner &O) {
     S->dim_rows = R;
     S->columns = (int32_t)src.size();
 
-    // ---- the attached columns: type, IntInfo, dictionary id for id; storage by concat's rule over dim's tracked extrema
+    // ---- the attached columns: type, IntInfo, dictionary id for id; storage by the storage rule over dim's tracked extrema
     const size_t nc = src.size();
     std::vector<Column *> att(nc);
     for (size_t k = 0; k < nc; k++) {
@@ -426,7 +364,7 @@ int run(Table *t, const sybl_lookup_desc *d, TableOwner &O) {
         n->dict = c->dict;
         n->dict_ix = c->dict_ix;
         n->elem = n->canon();
-        if (o->compact_mode && c->type != SYBL_SET_VAL) concat_fit(n.get(), c->n_pop > 0 && c->d_data, c->exact_min, c->exact_max, &n->elem, &n->vbase);
+        if (o->compact_mode && c->type != SYBL_SET_VAL) fit_storage(n->canon(), c->n_pop > 0 && c->d_data, c->exact_min, c->exact_max, &n->elem, &n->vbase);
         att[k] = n.get();
         o->col_ix[n->name] = (int)o->cols.size();
         o->cols.push_back(std::move(n));
@@ -439,7 +377,7 @@ int run(Table *t, const sybl_lookup_desc *d, TableOwner &O) {
     hipEvent_t ev[5];
     unsigned long long *counters = nullptr, h_counters[3] = {0, 0, 0};
     uint32_t *match = nullptr;
-    LkBlk *d_dblk = nullptr, *d_oblk = nullptr;
+    RowBlk *d_dblk = nullptr, *d_oblk = nullptr;
     int32_t *d_lut = nullptr;
     std::vector<int32_t> lut;
     if ((rc = pool.alloc(&counters, 3, "lookup counters"))) return rc;
@@ -447,14 +385,14 @@ int run(Table *t, const sybl_lookup_desc *d, TableOwner &O) {
     SYBL_HIP(hipMemsetAsync(counters, 0, 3 * sizeof(unsigned long long), st));
     Column *ok = o->find(kname);  // t's key column as the output holds it
     if (path) {
-        std::vector<LkBlk> oblk;
-        for (const Segment &b : o->blocks) oblk.push_back(LkBlk{b.start, b.n, 0});
+        std::vector<RowBlk> oblk;
+        for (const Segment &b : o->blocks) oblk.push_back(RowBlk{b.start, b.n, 0});
         if ((rc = pool.alloc(&d_dblk, dblk.size(), "lookup blocks"))) return rc;
         if ((rc = pool.alloc(&d_oblk, oblk.size(), "lookup blocks"))) return rc;
         if ((rc = pool.alloc(&T.first_row, (size_t)cells, "lookup cells"))) return rc;
         if (path == kLkHash && (rc = pool.alloc(&T.keys, (size_t)slots, "lookup hash keys"))) return rc;
-        if ((rc = host_to_device(ctx, d_dblk, dblk.data(), dblk.size() * sizeof(LkBlk), "lookup blocks"))) return rc;
-        if ((rc = host_to_device(ctx, d_oblk, oblk.data(), oblk.size() * sizeof(LkBlk), "lookup blocks"))) return rc;
+        if ((rc = host_to_device(ctx, d_dblk, dblk.data(), dblk.size() * sizeof(RowBlk), "lookup blocks"))) return rc;
+        if ((rc = host_to_device(ctx, d_oblk, oblk.data(), oblk.size() * sizeof(RowBlk), "lookup blocks"))) return rc;
         if (path == kLkStr) {  // t's dictionary id -> dim's, or -1 (the output holds t's dictionary id for id)
             lut.resize(std::max<size_t>(ok->dict.size(), 1), -1);
             for (size_t i = 0; i < ok->dict.size(); i++) {
@@ -470,17 +408,13 @@ int run(Table *t, const sybl_lookup_desc *d, TableOwner &O) {
         SYBL_HIP(hipMemsetAsync(T.first_row, 0xFF, (size_t)cells * 4, st));
         if (path == kLkHash) SYBL_HIP(hipMemsetAsync(T.keys, 0xFF, (size_t)slots * 8, st));
         const KeySide bs{dk->d_data, dk->vbase, dk->d_valid, d_dblk, (int)dblk.size(), R};
-#define LK_BUILD(W) launch_build<W>(path, bs, T, counters, st)
-        LK_BY_WIDTH(dk->elem, LK_BUILD)
-#undef LK_BUILD
+        by_width(dk->elem, [&](auto W) { launch_build<decltype(W)::value>(path, bs, T, counters, st); });
         SYBL_HIP(hipGetLastError());
         if ((rc = pool.event(&ev[1], st))) return rc;
 
         // ---- probe
         const KeySide ps{ok->d_data, ok->vbase, ok->d_valid, d_oblk, (int)oblk.size(), n_out};
-#define LK_PROBE(W) launch_probe<W>(path, ps, T, d_lut, (int64_t)ok->dict.size(), match, counters, st)
-        LK_BY_WIDTH(ok->elem, LK_PROBE)
-#undef LK_PROBE
+        by_width(ok->elem, [&](auto W) { launch_probe<decltype(W)::value>(path, ps, T, d_lut, (int64_t)ok->dict.size(), match, counters, st); });
         SYBL_HIP(hipGetLastError());
         if ((rc = pool.event(&ev[2], st))) return rc;
         uint32_t side = kLkNone;  // (hash: the side cell of the key -1)
@@ -509,11 +443,10 @@ int run(Table *t, const sybl_lookup_desc *d, TableOwner &O) {
     // ---- gather: every attached column whole, into its final place
     if ((rc = table_upload_blocks(o))) return rc;
     if ((rc = pool.event(&ev[3], st))) return rc;
-    int64_t n_stat = 0;
+    size_t n_stat = 0;
     for (size_t k = 0; k < nc; k++) n_stat += att[k]->type != SYBL_SET_VAL;
-    int64_t *d_stats = nullptr;
-    if (n_stat && (rc = pool.alloc(&d_stats, (size_t)n_stat * 3 * (size_t)nb_out, "lookup statistics"))) return rc;
-    int64_t j = 0;
+    BlockStats stats;
+    if ((rc = stats.begin(n_stat, o->d_blocks, nb_out, pool, "lookup statistics"))) return rc;
     for (size_t k = 0; k < nc; k++) {
         const Column *c = src[k];
         Column *n = att[k];
@@ -536,38 +469,15 @@ int run(Table *t, const sybl_lookup_desc *d, TableOwner &O) {
             SYBL_HIP(hipMemsetAsync(n->d_data, 0, (size_t)n_out * (size_t)n->elem, st));
             S->gather_bytes += n_out * (int64_t)n->elem;
         } else {
-#define LK_GATHER(W) launch_gather_to<W>(c, match, n_out, n, st)
-            LK_BY_WIDTH(c->elem, LK_GATHER)
-#undef LK_GATHER
+            by_width(c->elem, [&](auto WS) {
+                by_width(n->elem, [&](auto WD) { launch_gather<decltype(WS)::value, decltype(WD)::value>(c, match, n_out, n, st); });
+            });
             SYBL_HIP(hipGetLastError());
             S->gather_bytes += n_out * (4 + (int64_t)n->elem) + S->matched * (int64_t)c->elem + (c->d_valid ? S->matched * 4 : 0);
         }
-        int64_t *out = d_stats + j++ * 3 * nb_out;
-        hipError_t e = launch_block_minmax(n->d_data, n->elem, n->vbase, n->d_valid, o->d_blocks, (int)nb_out, out, out + nb_out, out + 2 * nb_out, st);
-        if (e != hipSuccess) return hip_fail(e, "k_block_minmax");
+        if ((rc = stats.launch(n, st))) return rc;  // (behind its gather: the column is read back from the cache)
     }
-    if ((rc = pool.event(&ev[4], st))) return rc;
-    std::vector<int64_t> stats((size_t)n_stat * 3 * (size_t)nb_out);
-    if (n_stat) SYBL_HIP(hipMemcpyAsync(stats.data(), d_stats, stats.size() * 8, hipMemcpyDeviceToHost, st));
-    SYBL_HIP(hipStreamSynchronize(st));  // the ONE wait for the statistics of every block of every attached column
-
-    j = 0;
-    for (size_t k = 0; k < nc; k++) {
-        Column *n = att[k];
-        if (n->type == SYBL_SET_VAL) continue;
-        const int64_t *h = stats.data() + j++ * 3 * nb_out;
-        n->blk_min.assign(h, h + nb_out);
-        n->blk_max.assign(h + nb_out, h + 2 * nb_out);
-        n->blk_pop.assign(h + 2 * nb_out, h + 3 * nb_out);
-        for (int64_t b = 0; b < nb_out; b++) {
-            if (n->blk_pop[(size_t)b] > 0) {
-                n->exact_min = std::min(n->exact_min, n->blk_min[(size_t)b]);
-                n->exact_max = std::max(n->exact_max, n->blk_max[(size_t)b]);
-            }
-            n->n_pop += n->blk_pop[(size_t)b];
-        }
-        n->stats_blocks = nb_out;
-    }
+    if ((rc = stats.finish(st, pool, &ev[4]))) return rc;  // the ONE wait for the statistics of every block of every attached column
 
     // ---- set columns: the host CSR over the output's physical rows, from the match list
     bool any_set = false;
@@ -580,13 +490,7 @@ int run(Table *t, const sybl_lookup_desc *d, TableOwner &O) {
             Column *n = att[k];
             if (c->type != SYBL_SET_VAL) continue;
             n->h_set_off.assign(1, 0);
-            n->h_set_off.reserve((size_t)phys_out + 1);
-            for (int64_t p = 0; p < phys_out; p++) {  // (padding rows match nothing: empty sets)
-                const size_t s = hm[(size_t)p];
-                if (hm[(size_t)p] != kLkNone && s + 1 < c->h_set_off.size())
-                    n->h_set_vals.insert(n->h_set_vals.end(), c->h_set_vals.begin() + c->h_set_off[s], c->h_set_vals.begin() + c->h_set_off[s + 1]);
-                n->h_set_off.push_back((int64_t)n->h_set_vals.size());
-            }
+            set_gather(c->h_set_off, c->h_set_vals, hm.data(), phys_out, n->h_set_off, n->h_set_vals);  // (padding rows match nothing: empty sets)
             n->set_dirty = true;
             if ((rc = column_upload_set(o, n))) return rc;
         }
@@ -607,24 +511,8 @@ int run(Table *t, const sybl_lookup_desc *d, TableOwner &O) {
 }  // namespace
 
 int lookup_run(Table *t, const sybl_lookup_desc *d, sybl_table **out) {
-    Ctx *ctx = t->ctx;
-    SYBL_HIP(hipSetDevice(ctx->device));
-    TableOwner O;
-    int rc;
-    try {
-        rc = run(t, d, O);
-    } catch (const std::bad_alloc &) {
-        rc = fail(SYBL_E_NOMEM, "sybl_table_lookup: out of host memory");
-    } catch (const std::exception &e) {
-        rc = fail(SYBL_E_INVAL, "sybl_table_lookup: %s", e.what());
-    }
-    if (rc) {
-        (void)hipStreamSynchronize(ctx->stream);  // (nothing of this call is in flight when its buffers go)
-        return rc;
-    }
-    *out = O.t;
-    O.t = nullptr;
-    return SYBL_OK;
+    TableOwner O;  // (run makes the table: the copy of t)
+    return derived_call(t->ctx, "sybl_table_lookup", O, out, [&] { return run(t, d, O); });
 }
 
 }  // namespace sybl

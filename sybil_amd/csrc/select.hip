@@ -13,15 +13,14 @@
 //                 exclusive popcount scan (within the wave by shuffles, across the waves through LDS): the structure of
 //                 k_smp_compact.  The matching rows' physical row numbers go to rows[rank], ascending: no atomics, every
 //                 position is written exactly once.
-//   gather        gather_rows (gather.h, digest.hip): the row list is a permutation for digest's machinery.
+//   gather        gather_rows (derived.h, digest.hip): the row list is a permutation for digest's machinery.
+// The call wrapper and the column list are derived.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <new>
 
 #include "bitmap_rank.h"
-#include "engine.h"
-#include "gather.h"
+#include "derived.h"
 
 namespace sybl {
 
@@ -87,15 +86,7 @@ int run(Table *t, const sybl_select_desc *d, int64_t block_rows, Table *o, sybl_
 
     // ---- the output's columns (NULL / 0: every column), each once, in the order named
     std::vector<Column *> src;
-    if (d->columns && d->n_columns > 0) {
-        for (int i = 0; i < d->n_columns; i++) {
-            Column *c = t->find(d->columns[i]);
-            if (!c) return fail(SYBL_E_INVAL, "select: unknown column '%s'", d->columns[i] ? d->columns[i] : "(null)");
-            if (std::find(src.begin(), src.end(), c) == src.end()) src.push_back(c);
-        }
-    } else {
-        for (auto &cp : t->cols) src.push_back(cp.get());
-    }
+    if ((rc = resolve_columns(t, d->columns, d->n_columns, "select", "", nullptr, &src))) return rc;
 
     // ---- filters, lowered by the planner
     struct FilterPlan {
@@ -231,27 +222,10 @@ int select_run(Table *t, const sybl_select_desc *d, sybl_table **out) {
     if (d->block_rows < 0 || d->block_rows > SYBL_BLOCK_ROWS)
         return fail(SYBL_E_INVAL, "select: block_rows %d is outside 0 .. %d", d->block_rows, SYBL_BLOCK_ROWS);
     const int64_t br = d->block_rows ? d->block_rows : SYBL_BLOCK_ROWS;
-    SYBL_HIP(hipSetDevice(t->ctx->device));
     TableOwner O;
-    O.t = new (std::nothrow) sybl_table();
-    if (!O.t) return fail(SYBL_E_NOMEM, "select: out of host memory");
-    O.t->ctx = t->ctx;
-    O.t->name = t->name;
-    int rc;
-    try {
-        rc = run(t, d, br, O.t, &O.t->select_stats);
-    } catch (const std::bad_alloc &) {
-        rc = fail(SYBL_E_NOMEM, "select: out of host memory");
-    } catch (const std::exception &e) {
-        rc = fail(SYBL_E_INVAL, "select: %s", e.what());
-    }
-    if (rc) {
-        (void)hipStreamSynchronize(t->ctx->stream);  // (nothing of this call is in flight when its buffers go)
-        return rc;
-    }
-    *out = O.t;
-    O.t = nullptr;
-    return SYBL_OK;
+    int rc = derived_new_table(t->ctx, t->name, "select", O);
+    if (rc) return rc;
+    return derived_call(t->ctx, "select", O, out, [&] { return run(t, d, br, O.t, &O.t->select_stats); });
 }
 
 }  // namespace sybl

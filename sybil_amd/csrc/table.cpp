@@ -8,11 +8,9 @@
 
 #include <algorithm>
 
-#include "engine.h"
+#include "derived.h"
 
 namespace sybl {
-
-static inline int64_t round_up(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 
 // Every copy of caller / heap memory into HBM on the append path (engine.h).  The bytes cross in pieces of the ctx's pinned
 // staging buffer -- the runtime's own staging of pageable hipMemcpyAsync sources is out of the picture --, each piece complete
@@ -137,38 +135,22 @@ int table_ensure_stats(Table *t) {
     hipStream_t st = t->ctx->stream;
     int urc = table_upload_blocks(t);
     if (urc) return urc;
+    GatherPool pool;  // (d_out goes on every exit; the allocation's error keeps the words it always had)
     int64_t *d_out = nullptr;
-    SYBL_HIP(hipMalloc((void **)&d_out, (size_t)nb * 3 * sizeof(int64_t)));
-    std::vector<int64_t> h((size_t)nb * 3);
+    if ((urc = pool.alloc(&d_out, (size_t)nb * 3, "hipMalloc((void **)&d_out, (size_t)nb * 3 * sizeof(int64_t))"))) return urc;
+    std::vector<int64_t> h((size_t)nb * 3), rows((size_t)nb);
+    for (int64_t b = 0; b < nb; b++) rows[(size_t)b] = t->blocks[(size_t)b].n;
     for (auto &cp : t->cols) {
         Column *c = cp.get();
         if (c->type == SYBL_SET_VAL || c->stats_blocks >= nb) continue;
         int64_t b0 = c->stats_blocks, n = nb - b0;
         hipError_t e = launch_block_minmax(c->d_data, c->elem, c->vbase, c->d_valid, t->d_blocks + b0, (int)n, d_out,
                                            d_out + nb, d_out + 2 * nb, st);
-        if (e != hipSuccess) {
-            hipFree(d_out);
-            return hip_fail(e, "k_block_minmax");
-        }
+        if (e != hipSuccess) return hip_fail(e, "k_block_minmax");
         SYBL_HIP(hipMemcpyAsync(h.data(), d_out, (size_t)nb * 3 * sizeof(int64_t), hipMemcpyDeviceToHost, st));
         SYBL_HIP(hipStreamSynchronize(st));
-        c->blk_min.resize((size_t)nb);
-        c->blk_max.resize((size_t)nb);
-        c->blk_pop.resize((size_t)nb);
-        for (int64_t k = 0; k < n; k++) {
-            c->blk_min[(size_t)(b0 + k)] = h[(size_t)k];
-            c->blk_max[(size_t)(b0 + k)] = h[(size_t)(nb + k)];
-            c->blk_pop[(size_t)(b0 + k)] = h[(size_t)(2 * nb + k)];
-            if (h[(size_t)(2 * nb + k)] > 0) {
-                c->exact_min = std::min(c->exact_min, h[(size_t)k]);
-                c->exact_max = std::max(c->exact_max, h[(size_t)(nb + k)]);
-            }
-            c->n_pop += h[(size_t)(2 * nb + k)];
-            if (h[(size_t)(2 * nb + k)] < t->blocks[(size_t)(b0 + k)].n) c->has_missing = true;
-        }
-        c->stats_blocks = nb;
+        stats_fold(col_stats(c, true), h.data(), nb, b0, n, rows.data() + b0);
     }
-    SYBL_HIP(hipFree(d_out));
     return SYBL_OK;
 }
 
@@ -418,22 +400,6 @@ int block_col_set_host(BlockWriter &w, Column *c, const int64_t *off, const int3
     return SYBL_OK;
 }
 
-// narrowest (width, base) that holds [lo, hi]; canonical storage when nothing narrower does
-static void fit_storage(const Column *c, bool any, int64_t lo, int64_t hi, int *width, int64_t *base) {
-    *width = c->canon();
-    *base = 0;
-    if (!any) {
-        *width = 1;  // no populated row: the stored bits are never looked at
-        return;
-    }
-    const unsigned __int128 range = (unsigned __int128)((__int128)hi - (__int128)lo);
-    int fit = range < 256 ? 1 : range < 65536 ? 2 : range < ((unsigned __int128)1 << 32) ? 4 : 8;
-    if (fit < *width) {
-        *width = fit;
-        *base = lo;
-    }
-}
-
 // Compact mode: the staged canonical blocks of the columns -> the columns' compact arrays.  The
 // block's exact extrema (one k_block_minmax launch per column, ONE readback for all of them) decide
 // whether a column's current (width, base) still holds every value; if not the resident rows are
@@ -502,12 +468,12 @@ static int commit_staged(BlockWriter &w) {
         if (!holds || !c->d_data) {
             int width;
             int64_t base;
-            fit_storage(c, any, lo, hi, &width, &base);
+            fit_storage(c->canon(), any, lo, hi, &width, &base);
             if (c->d_data && width < c->elem) {  // never narrow resident rows here (sybl_table_compact does)
                 width = c->elem;
                 base = c->elem == c->canon() ? 0 : std::min(lo, c->vbase);
                 if (c->elem < 8 && (__int128)hi > (__int128)base + (((__int128)1 << (8 * c->elem)) - 1))
-                    fit_storage(c, any, lo, hi, &width, &base);  // the old width cannot span the new range
+                    fit_storage(c->canon(), any, lo, hi, &width, &base);  // the old width cannot span the new range
             }
             if ((rc = column_repack(t, c, width, base))) return rc;
         }
@@ -519,16 +485,8 @@ static int commit_staged(BlockWriter &w) {
             if (e != hipSuccess) return hip_fail(e, "k_repack");
         }
         if (c->stats_blocks == nb) {
-            c->blk_min.push_back(bmin);
-            c->blk_max.push_back(bmax);
-            c->blk_pop.push_back(bpop);
-            if (bpop > 0) {
-                c->exact_min = std::min(c->exact_min, bmin);
-                c->exact_max = std::max(c->exact_max, bmax);
-            }
-            c->n_pop += bpop;
-            if (bpop < w.nrows) c->has_missing = true;
-            c->stats_blocks = nb + 1;
+            const int64_t one[3] = {bmin, bmax, bpop};
+            stats_fold(col_stats(c, true), one, 1, nb, 1, &w.nrows);
         }
     }
     return SYBL_OK;
@@ -542,16 +500,8 @@ int block_commit(BlockWriter &w) {
     for (auto &s : w.direct) {  // columns already in place: only their block statistics are left to record
         Column *c = s.c;
         if (c->stats_blocks != (int64_t)t->blocks.size()) continue;
-        c->blk_min.push_back(s.mn);
-        c->blk_max.push_back(s.mx);
-        c->blk_pop.push_back(s.pop);
-        if (s.pop > 0) {
-            c->exact_min = std::min(c->exact_min, s.mn);
-            c->exact_max = std::max(c->exact_max, s.mx);
-        }
-        c->n_pop += s.pop;
-        if (s.pop < w.nrows) c->has_missing = true;
-        c->stats_blocks = (int64_t)t->blocks.size() + 1;
+        const int64_t one[3] = {s.mn, s.mx, s.pop};
+        stats_fold(col_stats(c, true), one, 1, c->stats_blocks, 1, &w.nrows);
     }
     w.direct.clear();
     if (w.serial) {
@@ -1424,7 +1374,7 @@ static int compact_column(Table *t, Column *c) {
     if (c->type == SYBL_SET_VAL || !c->d_data) return SYBL_OK;
     int width;
     int64_t base;
-    fit_storage(c, c->n_pop > 0, c->exact_min, c->exact_max, &width, &base);
+    fit_storage(c->canon(), c->n_pop > 0, c->exact_min, c->exact_max, &width, &base);
     if (width >= c->elem) return SYBL_OK;  // already this narrow
     return column_repack(t, c, width, base);
 }

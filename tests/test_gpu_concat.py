@@ -660,6 +660,49 @@ def test_dead_blocks_contribute_nothing(ctx, tmp_path):
                 t.free()
 
 
+def test_three_runs_between_dead_blocks_are_transcoded(ctx, tmp_path):
+    """Live blocks of 33, 1 and 300 rows with a dead block between each pair: three runs of 64, 32 and 320 padded rows.  The second
+    source widens `row` and lowers the base of `time`, so k_cc_transcode walks the first source's run list -- both run boundaries
+    inside one wave, at 2 and 8 rows per lane -- and k_cc_valid its block list."""
+    blocks = []
+    for b, n in enumerate((33, 40, 1, 50, 300)):
+        i = np.arange(n)
+        blocks.append((n, {"time": ("int", ((i * 7919 + b * 13) % 500 - 100).astype(np.int64), (i % 5 != 0) | (n == 1)),
+                           "row": ("int", (i + 1000 * b).astype(np.int64)),
+                           "name": ("str", [None if k % 9 == 4 else "user%d" % (k % 50) for k in i])}))
+    j = np.arange(40)
+    wide = [(40, {"time": ("int", (j * 3 - 30000).astype(np.int64), j % 7 != 0),
+                  "row": ("int", (j + (1 << 20)).astype(np.int64)),
+                  "name": ("str", ["user%d" % (k % 50) for k in j])})]
+    root = str(tmp_path / "db")
+    F.write_table(root, "events", [cols for _, cols in blocks])
+    tb = ctx.open_table(root, "events", compact=True)
+    extra = build(ctx, wide, compact=True)
+    out = None
+    try:
+        shutil.rmtree(os.path.join(root, "events", "block%09d" % 2))
+        shutil.rmtree(os.path.join(root, "events", "block%09d" % 4))
+        assert tb.refresh()[1] == 2 and tb.rows == 334
+        live = [blocks[0], blocks[2], blocks[4]]
+        out = ctx.concat([tb, extra])
+        assert out.rows == 374 and out.blocks == 4
+        assert _rows(out) == D.rows_of(R.concat_ref([live, wide]))
+        st = out.concat_stats()
+        assert st["runs"] == 4 and st["transcodes"] >= 2, st
+        for name in ("time", "row"):                     # the first source does not have the output's stored form: it was transcoded
+            assert out.column_storage(name) != tb.column_storage(name), name
+        assert out.column_storage("row") == (4, 0) and out.column_storage("time")[0] == 2
+        n = out.rows
+        ref = D.concat(live + wide)
+        for name in ("time", "row"):
+            _, v, p = ref[name]
+            assert np.array_equal(out.read_int(name, 0, n)[p], v[p]), name
+    finally:
+        for t in (out, extra, tb):
+            if t is not None:
+                t.free()
+
+
 # ------------------------------------------------------------------ 10. the C example
 
 def test_c_example_runs(ctx, tmp_path):
