@@ -566,6 +566,7 @@ struct Query {
     bool fast_packed_n = false;  // ... the run-time-column-count form of the packed kernel (3-4 group columns)
     int fast_nf = 0, fast_ng = 0, fast_na = 0, fast_mode = 0;
     FastPlan fplan;
+    double late_estimate = 1.0;  // fill_packed's share of rows passing the range filters (the `late path:` trace line reports it)
     // partitioned histograms (strategy 5)
     bool part_hist = false, part_packed = false;
     int part_nf = 0, part_ng = 0, part_na = 0;

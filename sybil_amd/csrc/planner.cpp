@@ -122,6 +122,7 @@ static bool fill_packed(Table *t, Query *q, const std::vector<int> &slot_col, Fa
                 pass *= hi >= lo ? std::min(1.0, (hi - lo + 1.0) / (top + 1.0)) : 0.0;
             }
         }
+        q->late_estimate = pass;
         FP.late = nf > 0 && pass < 0.005 ? 1 : 0;
         if (const char *e = env("SYBL_LATE_PATH")) FP.late = atoi(e) != 0;  // (A/B: 0 / 1 whatever the estimate)
     }
@@ -1833,6 +1834,42 @@ struct Planner {
         return SYBL_OK;
     }
 
+    // SYBL_PLAN_TRACE=1 (diagnostic): `late path: kernel=hash_packed late=1 estimate=0.004` for every query that fills a packed
+    // plan -- the kernel family that will read it, whether the launch takes its late-materialisation form, and fill_packed's
+    // estimate of the share of rows passing.  late is the LAUNCH's: k_scan_hash_packed (hashed, and direct-mapped with run-time
+    // column counts: packed_n) and k_count_packed / k_emit_packed follow FastPlan::late where they have filters and no NUL body;
+    // k_scan_packed runs its late loop whatever the estimate (scan_packed.h: filters, something behind them, no NUL, no ring).
+    void trace_late_path() {
+        if (!env("SYBL_PLAN_TRACE")) return;
+        const char *kernel = nullptr;
+        int late = 0;
+        if (q->part_hist) {
+            if (!q->part_packed) return;
+            kernel = "count_emit";
+            late = q->part_nf > 0 && q->eplan.fp.late ? 1 : 0;
+        } else if (q->hash_mode) {
+            if (!q->hash_fast || !q->hash_packed) return;
+            kernel = "hash_packed";
+            late = q->fast_nf > 0 && q->fplan.late && !q->fplan.nul ? 1 : 0;
+        } else if (q->fast && q->fast_packed_n) {
+            kernel = "packed_n";
+            late = q->fast_nf > 0 && q->fplan.late && !q->fplan.nul ? 1 : 0;
+        } else if (q->fast && q->fast_packed) {
+            const FastPlan &FP = q->fplan;
+            kernel = "packed";
+            late = kPackedLate && !FP.nul && q->fast_nf > 0 && q->fast_ng + q->fast_na + (q->time_mode ? 1 : 0) > 0 ? 1 : 0;
+            // (SYBL_PACKED_RING=2 / 3 on the one filtered shape it is instantiated for: the ring loop, packed_launch_k1)
+            const char *ring = env("SYBL_PACKED_RING");
+            const bool g1 = FP.gwid[0] == 1 && FP.gwid[1] == 1;
+            if (ring && (atoi(ring) == 2 || atoi(ring) == 3) && !FP.dyn && !FP.lean && q->fast_nf == 3 && q->fast_ng == 2 && q->fast_na == 2 &&
+                q->fast_mode == kFastMoments && !q->time_mode && g1)
+                late = 0;
+        } else {
+            return;
+        }
+        fprintf(stderr, "late path: kernel=%s late=%d estimate=%.6g\n", kernel, late, q->late_estimate);
+    }
+
     int window() {
         int rc;
         // ---- LDS-window strategy: a time-series table too large for LDS, scanned by workgroups whose
@@ -1911,6 +1948,7 @@ struct Planner {
         plan_dynamic();  // (plan_count_packing and plan_lean, for the dealing it takes)
         if ((rc = plan_pushdown())) return rc;
         plan_narrow();
+        trace_late_path();
         q->stats.rows_scanned = rows_scanned;
         q->stats.blocks_skipped = skipped;
         q->stats.blocks_scanned = (int64_t)t->blocks.size() - skipped;
