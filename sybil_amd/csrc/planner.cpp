@@ -1891,11 +1891,17 @@ struct Planner {
             P.lds_cells = (int32_t)L;
             q->lds_bytes = (size_t)(L * 8 * (1 + F + M));
         }
+        // SYBL_PLAN_TRACE=1 (diagnostic): `window: windowed=1 wmax=3 cells=300 lds_cells=900 replicas=4 why=ok` for every
+        // direct-mapped time-series query -- the widest window in time buckets, the group cells of one bucket, the cells and
+        // replicas the launch gets, and why a query is not windowed: fits_lds (the whole table does), SYBL_NO_WINDOW, no_blocks,
+        // bounds (declared bounds narrower than the data), budget (wmax x cells x fields x 8 > kLdsBudgetBytes)
+        const char *why = q->use_lds ? "fits_lds" : env("SYBL_NO_WINDOW") ? "SYBL_NO_WINDOW" : t->blocks.empty() ? "no_blocks" : "ok";
+        int64_t wmax = 0;
         // (a hashed query keeps its staging table: the window below is a direct-mapped slice of [time bucket][cell])
         if (!q->use_lds && !q->hash_mode && q->time_mode && !env("SYBL_NO_WINDOW") && !t->blocks.empty()) {
             const Column *tc = slot_column(t, q, slot_col[(size_t)P.time_slot]);
             std::vector<int32_t> base((size_t)q->n_wg, 0);
-            int64_t wmax = 1;
+            wmax = 1;
             bool ok = true;
             for (int w = 0; w < q->n_wg && ok; w++) {
                 int64_t lo = INT64_MAX, hi = INT64_MIN;
@@ -1933,8 +1939,13 @@ struct Planner {
                 SYBL_HIP(hipMalloc((void **)&q->d_wg_cell_base, base.size() * 4));
                 SYBL_HIP(hipMemcpy(q->d_wg_cell_base, base.data(), base.size() * 4, hipMemcpyHostToDevice));
                 P.wg_cell_base = q->d_wg_cell_base;
+            } else {
+                why = ok ? "budget" : "bounds";
             }
         }
+        if (q->time_mode && !q->hash_mode && env("SYBL_PLAN_TRACE"))
+            fprintf(stderr, "window: windowed=%d wmax=%lld cells=%lld lds_cells=%d replicas=%d why=%s\n", (int)P.windowed, (long long)wmax,
+                    (long long)cells, (int)P.lds_cells, 1 << P.rep_shift, why);
         select_fast_path(t, q, slot_col);
         select_hash_fast(t, q, slot_col);
         prefilter_commit();

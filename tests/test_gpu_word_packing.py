@@ -15,7 +15,8 @@ evenly, so a table of n_wg * T * 4096 rows gives every workgroup exactly T packe
 numpy int64 / Python int computation over the whole column and holds whatever the split is.
 
 Not covered: the same boundary for 1- and 2-byte aggregation columns (sum_bits + count_bits reaches 64 only near 4e9 rows per
-workgroup set there), and the windowed flush (strategy 4) through sum_of.
+workgroup set there).  The windowed flush (strategy 4) through sum_of / max_of, for the plain, cshift and lean word layouts, is
+tests/test_gpu_time_window.py's.
 """
 import re
 
