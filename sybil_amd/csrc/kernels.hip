@@ -1176,8 +1176,7 @@ hipError_t launch_part_fix(const PartHistPlan &P, hipStream_t st) {
 
 template <int NA, bool TRACK_MAX>
 static hipError_t part_hist_launch(const PartHistPlan &P, size_t lds, hipStream_t st) {
-    bool out = false;  // a column whose bounds let a value land beyond the last bucket
-    for (int a = 0; a < NA; a++) out = out || P.f_out[a] >= 0;
+    const bool out = part_hist_out(P);  // a column whose bounds let a value land beyond the last bucket (NA == P.n_aggs)
     auto k = out ? k_part_hist<NA, TRACK_MAX, true> : k_part_hist<NA, TRACK_MAX, false>;
     hipError_t e = hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
@@ -1192,7 +1191,7 @@ hipError_t launch_part_hist(const PartHistPlan &P, hipStream_t st) {
     const uint32_t n_reg = ((uint32_t)P.n_wg + (uint32_t)P.split - 1u) / (uint32_t)P.split;
     size_t lds = (size_t)kPartCells * ((P.nv_max + 2) / 2) * 4 + (size_t)kPartCells * (kPartSumRep + 1) * 8 + (size_t)n_reg * 8 + 16 +  // + item / region cursors
                  (size_t)kPartCells * 48;  // + the pairs' outlier sums (OUT)
-    const bool track_max = P.m_max[0] >= 0 || (P.n_aggs > 1 && P.m_max[1] >= 0);
+    const bool track_max = part_hist_track_max(P);
     if (P.n_aggs == 1) return track_max ? part_hist_launch<1, true>(P, lds, st) : part_hist_launch<1, false>(P, lds, st);
     if (P.n_aggs == 2) return track_max ? part_hist_launch<2, true>(P, lds, st) : part_hist_launch<2, false>(P, lds, st);
     return hipErrorInvalidValue;

@@ -488,7 +488,7 @@ struct PartGeom {
     int64_t n_parts = 0, nb = 0, cap = 0, n_wg = 0;
     size_t wrap_cap = 0, table_words = 0;
 };
-static bool plan_part_pass(Table *t, Query *q, const std::vector<int> &slot_col, int64_t rows_scanned, int a0, int n, EmitPlan &E, PartGeom &G) {
+static const char *plan_part_pass(Table *t, Query *q, const std::vector<int> &slot_col, int64_t rows_scanned, int a0, int n, EmitPlan &E, PartGeom &G) {
     const ScanPlan &P = q->plan;
     bool any_max, all_max, gen;
     // (fill_fast_columns walks q->aggs: hand it the slice)
@@ -498,7 +498,7 @@ static bool plan_part_pass(Table *t, Query *q, const std::vector<int> &slot_col,
     const bool shape = fill_fast_columns(t, q, slot_col, E.fp, &G.nf, &G.ng, &G.na, &any_max, &all_max, false, &gen, &G.packed,
                                          kFastTemplatedG, kFastTemplatedA, true);
     q->aggs.swap(all);
-    if (!shape) return false;
+    if (!shape) return "shape";
     const int na = G.na;
     // (the emitting kernels subtract h.Min -- canonical storage -- or add adoff = base - h.Min -- compact storage: biased
     // by BucketSize, the record's value part comes out as v - h.Min + BucketSize at no cost)
@@ -511,8 +511,8 @@ static bool plan_part_pass(Table *t, Query *q, const std::vector<int> &slot_col,
     // (bucket + 1) x BucketSize in 24 bits
     for (int a = a0; a < a0 + n; a++) {
         const AggDesc &A = q->aggs[(size_t)a].d;
-        if (A.n_values > (1 << kBucketBits) || A.bucket_size >= ((int64_t)1 << 24)) return false;
-        if (((int64_t)A.n_values + 1) * A.bucket_size >= ((int64_t)1 << kRecValueBits)) return false;
+        if (A.n_values > (1 << kBucketBits) || A.bucket_size >= ((int64_t)1 << 24)) return "bucket";
+        if (((int64_t)A.n_values + 1) * A.bucket_size >= ((int64_t)1 << kRecValueBits)) return "bucket";
         if (A.f_out >= 0) {
             // outliers: every accepted value, not only the bucket range, must fit the record, and k_part_hist's quotient
             // (a 24-bit multiply checks it) stays below 2^24
@@ -520,18 +520,18 @@ static bool plan_part_pass(Table *t, Query *q, const std::vector<int> &slot_col,
             const int64_t hi = std::min(c->bounds_set ? c->bound_hi : c->exact_max, A.max10);
             if (hi < A.hmin) continue;
             const unsigned __int128 span = (unsigned __int128)((__int128)hi - (__int128)A.hmin) + (unsigned __int128)A.bucket_size;
-            if (span >= ((unsigned __int128)1 << kRecValueBits) - 1 || span / (unsigned __int128)A.bucket_size >= ((unsigned __int128)1 << 24)) return false;
+            if (span >= ((unsigned __int128)1 << kRecValueBits) - 1 || span / (unsigned __int128)A.bucket_size >= ((unsigned __int128)1 << 24)) return "span";
         }
     }
     int64_t pairs = (int64_t)P.n_cells * na;
     G.n_parts = (pairs + kPartCells - 1) / kPartCells;
-    if (G.n_parts > kMaxParts) return false;
+    if (G.n_parts > kMaxParts) return "pairs";
     // Staging bins: a partition is spread over 1 << ss bins (a lane's bin follows from its lane number) so that
     // few partitions do not serialise on a handful of LDS counters; fewer bins when a workgroup's share of
     // the records would leave most of a bin's chunks padding.
     const int64_t recs_all = rows_scanned * na;
     G.n_wg = std::max(1, q->n_wg);
-    if (G.n_wg > 2048) return false;  // k_part_hist keeps one region descriptor per scanning workgroup in LDS
+    if (G.n_wg > 2048) return "n_wg";  // k_part_hist keeps one region descriptor per scanning workgroup in LDS
     int ss = 0;
     while ((G.n_parts << (ss + 1)) <= kEmitMaxBins) ss++;
     while (ss > 0 && recs_all / (G.n_wg * (G.n_parts << ss)) < 64) ss--;
@@ -541,7 +541,7 @@ static bool plan_part_pass(Table *t, Query *q, const std::vector<int> &slot_col,
     // 32-bit byte offset below kEmitDropOffset (2 GiB).
     G.nb = G.n_parts << ss;
     G.cap = recs_all + G.n_wg * G.nb * (int64_t)kEmitChunk + kEmitChunk;
-    if (G.cap >= ((int64_t)1 << 32) - ((int64_t)1 << 22)) return false;
+    if (G.cap >= ((int64_t)1 << 32) - ((int64_t)1 << 22)) return "cap";
     int64_t wg_rows_max = 0;
     {
         std::vector<int64_t> per_wg((size_t)G.n_wg, 0);
@@ -549,11 +549,11 @@ static bool plan_part_pass(Table *t, Query *q, const std::vector<int> &slot_col,
             for (int si = q->wg_seg_begin[(size_t)w]; si < q->wg_seg_begin[(size_t)w + 1]; si++) per_wg[(size_t)w] += q->segs[(size_t)si].n;
         for (int64_t v : per_wg) wg_rows_max = std::max(wg_rows_max, v);
     }
-    if ((wg_rows_max * na + G.nb * (int64_t)kEmitChunk) * 4 >= (int64_t)kEmitDropOffset) return false;
+    if ((wg_rows_max * na + G.nb * (int64_t)kEmitChunk) * 4 >= (int64_t)kEmitDropOffset) return "cap";
     // k_part_hist's 16-bit bucket counters log their wraps: at most 3 entries per 65536 records (kernels.hip)
     G.wrap_cap = (size_t)(3 * (recs_all / 65536 + 1) + 4096);
     G.table_words = (size_t)G.n_wg * (size_t)(G.nb + 1) + (size_t)G.n_wg + 1 + 2 + 2 * G.wrap_cap;
-    return true;
+    return nullptr;
 }
 
 // ... and its plans over the (shared) buffers
@@ -612,8 +612,20 @@ static int select_part_hist(Table *t, Query *q, const std::vector<int> &slot_col
     if (q->fast && q->fplan.hist_lds) return SYBL_OK;  // the bucket arrays already live in LDS
     // k_emit / k_part_hist take one or two aggregations: a query with three or four runs the sequence twice (same rows,
     // same buffers; every pass fills its own aggregations' bucket arrays and sum fields of the one cell table)
+    // SYBL_PLAN_TRACE=1 (diagnostic): one `part hist: pass=0 aggs=2 packed=1 nf=0 ng=1 parts=1024 ss=0 bins=1024 n_wg=256 split=1
+    // track_max=0 out=0 count_key=1` per pass of a query that takes the strategy -- the partitions, the staging bins per partition
+    // (1 << ss) and in all, the scanning workgroups, the shares of a partition, and what the launchers will instantiate:
+    // k_part_hist<aggs, track_max, out>, and k_count_key (1) or k_count / k_count_packed (0) -- or `part hist: rejected why=...`
+    // for a full-histogram query left to another strategy: shape (columns or filters the row bodies do not take), bucket (the
+    // record's 26 value bits or the 24-bit bucket product), span (the same for outliers), pairs (more than kMaxParts
+    // partitions), n_wg, cap (record buffer offsets), memory.
+    const bool plan_trace = env("SYBL_PLAN_TRACE") != nullptr;
+    auto rejected = [&](const char *why) {
+        if (plan_trace) fprintf(stderr, "part hist: rejected why=%s\n", why);
+        return SYBL_OK;
+    };
     const int n_all = (int)q->aggs.size();
-    if (n_all > kFastMaxA) return SYBL_OK;
+    if (n_all > kFastMaxA) return rejected("shape");
     const int n_pass = (n_all + kFastTemplatedA - 1) / kFastTemplatedA;
     std::vector<PartGeom> geo((size_t)n_pass);
     std::vector<EmitPlan> eps((size_t)n_pass);
@@ -621,12 +633,12 @@ static int select_part_hist(Table *t, Query *q, const std::vector<int> &slot_col
     for (int p = 0; p < n_pass; p++) {
         const int a0 = p * kFastTemplatedA, n = std::min(kFastTemplatedA, n_all - a0);
         memset(&eps[(size_t)p], 0, sizeof(EmitPlan));
-        if (!plan_part_pass(t, q, slot_col, rows_scanned, a0, n, eps[(size_t)p], geo[(size_t)p])) return SYBL_OK;
+        if (const char *why = plan_part_pass(t, q, slot_col, rows_scanned, a0, n, eps[(size_t)p], geo[(size_t)p])) return rejected(why);
         rec_words = std::max(rec_words, (size_t)geo[(size_t)p].cap);
         table_words = std::max(table_words, geo[(size_t)p].table_words);
     }
     size_t bytes = rec_words * 4 + table_words * 4, free_b = 0, total_b = 0;
-    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes + ((size_t)1 << 30) > free_b) return SYBL_OK;
+    if (hipMemGetInfo(&free_b, &total_b) != hipSuccess || bytes + ((size_t)1 << 30) > free_b) return rejected("memory");
     SYBL_HIP(hipMalloc((void **)&q->d_recs, rec_words * 4));
     // boff | wbase | wrap log in one allocation
     SYBL_HIP(hipMalloc((void **)&q->d_cursor, table_words * 4));
@@ -645,6 +657,16 @@ static int select_part_hist(Table *t, Query *q, const std::vector<int> &slot_col
         q->part_more.push_back(pp);
     }
     q->part_hist = true;
+    if (plan_trace) {
+        for (int p = 0; p < n_pass; p++) {
+            const EmitPlan &E = p ? q->part_more[(size_t)p - 1].E : q->eplan;
+            const PartHistPlan &H = p ? q->part_more[(size_t)p - 1].H : q->pplan;
+            const PartGeom &G = geo[(size_t)p];
+            fprintf(stderr, "part hist: pass=%d aggs=%d packed=%d nf=%d ng=%d parts=%d ss=%d bins=%lld n_wg=%d split=%d track_max=%d out=%d count_key=%d\n", p,
+                    (int)H.n_aggs, G.packed ? 1 : 0, q->part_nf, q->part_ng, (int)H.n_parts, (int)H.sub_shift, (long long)G.nb, (int)H.n_wg, (int)H.split,
+                    part_hist_track_max(H) ? 1 : 0, part_hist_out(H) ? 1 : 0, G.packed && count_takes_key_kernel(E, q->part_nf, q->part_ng) ? 1 : 0);
+        }
+    }
     return SYBL_OK;
 }
 

@@ -322,6 +322,21 @@ hipError_t launch_part_hist(const PartHistPlan &P, hipStream_t st);
 hipError_t launch_prefilter(const ScanPlan *d_plan, int n_slots, uint32_t *bits, int n_wg, hipStream_t st);
 hipError_t launch_part_fix(const PartHistPlan &P, hipStream_t st);
 
+// What the launchers of strategy 5 decide on the host, in one place: launch_part_hist / part_hist_launch (kernels.hip) and
+// count_packed_launch_nf (scan_packed.h) call these, and so does the planner's `part hist:` trace line.
+// k_part_hist<NA, TRACK_MAX, OUT>: some aggregation of the pass tracks its maximum / may see a value beyond its last bucket
+inline bool part_hist_track_max(const PartHistPlan &P) { return P.m_max[0] >= 0 || (P.n_aggs > 1 && P.m_max[1] >= 0); }
+inline bool part_hist_out(const PartHistPlan &P) {
+    bool out = false;
+    for (int a = 0; a < P.n_aggs; a++) out = out || P.f_out[a] >= 0;
+    return out;
+}
+// k_count_key instead of k_count_packed (compact storage): one key column of 1, 2 or 4 stored bytes, no filter, one bin per partition
+inline bool count_takes_key_kernel(const EmitPlan &E, int nf, int ng) {
+    if (nf != 0 || ng != 1 || E.sub_shift != 0 || env("SYBL_NO_COUNT16")) return false;
+    return E.fp.gwid[0] == 1 || E.fp.gwid[0] == 2 || E.fp.gwid[0] == 4;
+}
+
 #ifdef __HIPCC__
 
 typedef long long fll2 __attribute__((ext_vector_type(2)));

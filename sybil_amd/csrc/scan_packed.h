@@ -1302,7 +1302,7 @@ __global__ __launch_bounds__(kWgThreads, 4) void k_count_key(const EmitPlan E) {
 template <int NF>
 static hipError_t count_packed_launch_nf(const EmitPlan &E, int ng, int n_wg, hipStream_t st) {
     const size_t lds = count_lds_bytes(E);
-    if (NF == 0 && ng == 1 && E.sub_shift == 0 && !env("SYBL_NO_COUNT16")) {
+    if (count_takes_key_kernel(E, NF, ng)) {
         switch (E.fp.gwid[0]) {
         case 1: hipLaunchKernelGGL((k_count_key<1>), dim3(n_wg), dim3(kWgThreads), lds, st, E); return hipGetLastError();
         case 2: hipLaunchKernelGGL((k_count_key<2>), dim3(n_wg), dim3(kWgThreads), lds, st, E); return hipGetLastError();

@@ -106,7 +106,7 @@ def test_cfg4_global_atomic_strategy(ctx, oracle, monkeypatch):
 
 
 def test_all_rows_in_one_partition(ctx, oracle):
-    """All rows land in ONE of 2048 partitions (declared bounds far wider than the data).  The partition
+    """All rows land in ONE of 1024 partitions (declared bounds far wider than the data).  The partition
     buffers are sized by the counting pass, so badly skewed keys need no overflow handling: the query
     stays on the partitioned-histogram strategy and the results are unchanged."""
     from sybil_amd import synth
