@@ -112,6 +112,7 @@ static void free_query(Query *q) {
     }
     q->eff_weight.reset();  // (shared with the weight column's cache: freed with its last holder)
     q->fword.reset();       // (shared with the table's filter words and the other queries that read this one, likewise)
+    q->kword.reset();       // (the key word, likewise)
     if (q->d_plan) hipFree(q->d_plan);
     if (q->d_preplan) hipFree(q->d_preplan);
     if (q->d_prebits) hipFree(q->d_prebits);

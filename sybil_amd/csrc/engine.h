@@ -208,6 +208,7 @@ struct LoadedBlock {
 // and a prepared query holds its own share (Query::fword): a word that is evicted or replaced is freed by its last holder.
 struct FilterWord {
     std::vector<int> cols;  // table column indices, ascending: the key, and the order of the fields
+    int agg = -1;           // a key word (Table::kwords): which of cols is the plan's aggregation 0, part of the key; -1 = a filter word
     int n = 0;
     int32_t bits[kFwordMaxFields] = {}, shift[kFwordMaxFields] = {};
     int elem[kFwordMaxFields] = {};       // the columns' stored widths and bases the words were packed from
@@ -250,6 +251,7 @@ struct Table {
     std::vector<Query *> queries;  // prepared queries that are alive (a table that goes away first has their pending lazy results built)
     std::vector<std::shared_ptr<FilterWord>> fwords;  // the filter words this table holds (table_build_fword)
     uint64_t fword_clock = 0;
+    std::vector<std::shared_ptr<FilterWord>> kwords;  // the key words this table holds (table_build_kword): a list and a cap of their own
     Column *find(const char *name) const;
 };
 
@@ -271,6 +273,8 @@ void column_drop_narrow(Column *c);
 // The filter word of columns cols[0 .. n) (table column indices, any order, no duplicates) for the current table version, or
 // nullptr: the set is not eligible, the feature is off, or HBM is short (never an error of the query: the plan keeps the columns)
 std::shared_ptr<FilterWord> table_build_fword(Table *t, const int *cols, int n);
+// The key word of key columns keys[0 .. n_keys) and aggregation column agg, likewise (table.cpp: the filter words' builder)
+std::shared_ptr<FilterWord> table_build_kword(Table *t, const int *keys, int n_keys, int agg);
 int column_install_gdict(Table *t, Column *c);         // sorted gdict -> device value->rank map
 int column_repack(Table *t, Column *c, int width, int64_t vbase);  // change the stored width in place
 
@@ -459,6 +463,7 @@ struct Query {
     // query's own that the scan reads in the weight column's place (planner.cpp: Planner::weight)
     std::shared_ptr<Column> eff_weight;  // (= the weight column's Column::carried_weight)
     std::shared_ptr<FilterWord> fword;   // the filter word fplan reads (planner.cpp: plan_fword), or none: this query's share of it
+    std::shared_ptr<FilterWord> kword;   // the key word fplan reads (planner.cpp: plan_kword), or none, likewise
     int printed_level = 0;      // sybl_query_desc.printed_only as given (2: the rows beyond the limit may carry their Count alone)
     bool printed_only = false;  // sybl_query_desc.printed_only: percentiles / stddev / bucket arrays for the printed rows + Cumulative only
     bool top_only = false;      // ... and this query is one it applies to (query_snapshot: summary shape, limit > 0)

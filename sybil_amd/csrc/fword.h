@@ -55,6 +55,11 @@ SYBL_HD uint32_t fword_pack(const uint32_t *offsets, int n, const int32_t *shift
 
 SYBL_HD uint32_t fword_field(uint32_t word, int shift, int bits) { return (word >> shift) & fword_mask(bits); }
 
+// The bytes a row of one column costs a scan that reads no word: the stored width, a 4-byte AGGREGATION column that has or can
+// get a narrow twin (narrow3.h: offsets below 2^24) counted at the twin's 3.  A word must save bytes over the sum of these, so
+// a set must cost at least 5: two 1-byte keys and a 20-bit aggregation do (5 -> 4), one 1-byte key and a 2-byte aggregation do not.
+SYBL_HD int word_bytes_today(int elem, uint32_t max_off, bool is_agg) { return is_agg && elem == 4 && max_off < (1u << 24) ? 3 : elem; }
+
 // what k_pack_fword reads (kernels.hip: launch_pack_fword): the n source columns in field order, each at its stored width
 struct FwordPack {
     const void *col[kFwordMaxFields];

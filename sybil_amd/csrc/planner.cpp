@@ -1770,18 +1770,62 @@ struct Planner {
         q->fword = std::move(w);
     }
 
+    // Key words (Table::kwords; table.cpp: table_build_kword): when the launch is k_scan_packed's DYNAMIC LATE loop -- filters a
+    // tile ahead, no NUL, not windowed, no time column -- and every key column and aggregation 0 are plain reads of the table's
+    // own stored int columns, the keys and aggregation 0 are read from one 4-byte word per row that holds their stored offsets
+    // as bit fields: config 3's two 1-byte keys and its first 20-bit aggregation cost 4 bytes a row instead of 5, and one full
+    // 16-byte load per lane instead of three.  The offsets are the columns': gdoff / adoff and every proof of
+    // plan_count_packing and plan_lean stand as they are, and gcol / gwid / gbase, acol[0] / awid[0] / abase[0] keep the stored
+    // columns' values -- no other kernel ever sees a word.  Only aggregation 0 is a candidate: the kernel never asks, per column
+    // and tile, where its values come from.  It must land on an instantiated kernel (scan_packed.h: the KW kernels have one
+    // filter column, or a filter word).
+    void plan_kword() {
+        FastPlan &FP = q->fplan;
+        FP.kword = nullptr;
+        q->kword.reset();
+        if (!kPackedLate || !q->dyn || FP.nul || P.windowed || q->time_mode || q->fast_nf < 1 || q->fast_ng < 1 || q->fast_na < 1) return;
+        if (q->fast_ng + 1 > kFwordMaxFields || q->fast_ng > kFastTemplatedG || q->fast_na > kFastTemplatedA) return;
+        if ((q->fast_nf >= kFwordMinFields) != (FP.fword != nullptr)) return;  // (no such kernel)
+        if (FP.wcol || FP.f_out[0] >= 0 || FP.f_cnt[0] >= 0 || FP.f_pop[0] >= 0 || FP.avalid[0]) return;
+        auto stored = [&](const void *p, int wid, int64_t base) -> int {
+            for (size_t i = 0; i < t->cols.size(); i++)
+                if (t->cols[i]->d_data && t->cols[i]->d_data == p) return wid == t->cols[i]->elem && base == t->cols[i]->vbase ? (int)i : -1;
+            return -1;  // (a derived column -- ranks, a twin -- in the column's place)
+        };
+        int keys[kFastMaxG];
+        for (int c = 0; c < q->fast_ng; c++) {
+            keys[c] = FP.gvalid[c] ? -1 : stored(FP.gcol[c], FP.gwid[c], FP.gbase[c]);
+            if (keys[c] < 0) return;
+        }
+        const int agg = stored(FP.acol[0], FP.awid[0], FP.abase[0]);
+        if (agg < 0) return;
+        std::shared_ptr<FilterWord> w = table_build_kword(t, keys, q->fast_ng, agg);
+        if (!w) return;
+        auto field = [&](int col) { return (int)(std::find(w->cols.begin(), w->cols.end(), col) - w->cols.begin()); };
+        for (int c = 0; c < q->fast_ng; c++) {
+            FP.gshift[c] = w->shift[field(keys[c])];
+            FP.gbits[c] = w->bits[field(keys[c])];
+        }
+        FP.kashift = w->shift[field(agg)];
+        FP.kabits = w->bits[field(agg)];
+        FP.kword = (const uint32_t *)w->d_data;
+        q->kword = std::move(w);
+    }
+
     // Narrow twins (Column::narrow; table.cpp: column_build_narrow): once the strategy is final and the launch is k_scan_packed's
     // -- plain, windowed, NUL, static or dynamic -- every aggregation column that has (or can get) a twin is read from it: 3 bytes
     // a row instead of 4.  The twin keeps the column's base, so abase / adoff / the proofs of plan_count_packing and plan_lean
     // stand as they are; validity words stay the column's.  Filter, key and time columns, and every other kernel that reads
     // FastPlan / EmitPlan widths (hash, pushdown, count / emit, the pre-pass, GEN), keep the stored column.
     // SYBL_PLAN_TRACE=1: `narrow: a0=3 a1=3 bytes_per_row=14` -- the width each aggregation is read at and the bytes a row costs;
-    // with a filter word (plan_fword) `narrow: f=word(10,10,10) a0=3 a1=3 bytes_per_row=12`.
+    // with a filter word (plan_fword) `narrow: f=word(10,10,10) a0=3 a1=3 bytes_per_row=12`; with a key word besides (plan_kword)
+    // `narrow: f=word(10,10,10) k=word(4,6,20) a1=3 bytes_per_row=11` -- aggregation 0 then gets no twin: nothing would read it.
     void plan_narrow() {
         if (!(q->fast && q->fast_packed && !q->fast_packed_n && !q->hash_mode && !q->part_hist)) return;
         FastPlan &FP = q->fplan;
         plan_fword();
-        for (int a = 0; a < q->fast_na; a++) {
+        plan_kword();
+        for (int a = FP.kword ? 1 : 0; a < q->fast_na; a++) {
             Column *c = t->cols[(size_t)q->aggs[(size_t)a].col].get();
             if (FP.awid[a] != 4 || (const void *)FP.acol[a] != c->d_data || FP.abase[a] != c->vbase) continue;
             if (Column *n = column_build_narrow(t, c)) {
@@ -1792,7 +1836,7 @@ struct Planner {
         if (env("SYBL_PLAN_TRACE")) {
             int bytes = q->time_mode ? FP.twid : 0;
             for (int c = 0; c < q->fast_nf; c++) bytes += FP.fword ? 0 : FP.fwid[c];
-            for (int c = 0; c < q->fast_ng; c++) bytes += FP.gwid[c];
+            for (int c = 0; c < q->fast_ng; c++) bytes += FP.kword ? 0 : FP.gwid[c];
             std::string line = "narrow:";
             if (FP.fword) {  // (plan_fword) the filters, as the bits of each one's field: `f=word(10,10,10)`
                 bytes += 4;
@@ -1800,7 +1844,13 @@ struct Planner {
                 for (int c = 0; c < q->fast_nf; c++) line += (c ? "," : "") + std::to_string(FP.fbits[c]);
                 line += ")";
             }
-            for (int a = 0; a < q->fast_na; a++) {
+            if (FP.kword) {  // (plan_kword) the keys and aggregation 0, as the bits of each one's field: `k=word(4,6,20)`
+                bytes += 4;
+                line += " k=word(";
+                for (int c = 0; c < q->fast_ng; c++) line += std::to_string(FP.gbits[c]) + ",";
+                line += std::to_string(FP.kabits) + ")";
+            }
+            for (int a = FP.kword ? 1 : 0; a < q->fast_na; a++) {
                 bytes += FP.awid[a];
                 line += " a" + std::to_string(a) + "=" + std::to_string(FP.awid[a]);
             }

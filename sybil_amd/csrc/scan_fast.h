@@ -132,6 +132,12 @@ struct FastPlan {
     // nullptr = the columns.  fcol / fwid / fbase stay the stored columns' values: no other kernel ever sees a word.
     const uint32_t *fword;
     int32_t fshift[kFastMaxF], fbits[kFastMaxF];
+    // k_scan_packed's dynamic late loop (the KW instantiations; planner.cpp: plan_kword): the stored offsets of every key column
+    // and of aggregation 0 read from ONE 4-byte word per row (a key word: a filter word in layout, fword.h) -- key c is the field
+    // of gbits[c] bits at gshift[c], aggregation 0 the field of kabits bits at kashift -- instead of from gcol[] and acol[0].
+    // nullptr = the columns.  gcol / gwid / gbase and acol[0] / awid[0] / abase[0] stay the stored columns' values.
+    const uint32_t *kword;
+    int32_t gshift[kFastMaxG], gbits[kFastMaxG], kashift, kabits;
 };
 
 hipError_t launch_scan_fast(const FastPlan &P, int nf, int ng, int na, int mode, bool time, bool gen, int n_wg,
@@ -139,9 +145,10 @@ hipError_t launch_scan_fast(const FastPlan &P, int nf, int ng, int na, int mode,
 
 // A width of 3 is a narrow twin (narrow3.h), which only k_scan_packed decodes, and only as an aggregation column (planner.cpp:
 // plan_narrow).  Every other launcher that takes FastPlan widths refuses a plan that holds one (aggs = true), and
-// launch_scan_packed one that holds it anywhere else: an internal error, never a wrong answer.
+// launch_scan_packed one that holds it anywhere else: an internal error, never a wrong answer.  A key word (FastPlan::kword) is
+// k_scan_packed's alone in the same way: the other launchers (aggs = true) refuse a plan that holds one.
 inline bool fast_plan_has_narrow(const FastPlan &P, bool aggs) {
-    bool any = P.twid == 3 || P.wwid == 3;
+    bool any = P.twid == 3 || P.wwid == 3 || (aggs && P.kword != nullptr);
     for (int c = 0; c < kFastMaxF; c++) any = any || P.fwid[c] == 3;
     for (int c = 0; c < kFastMaxG; c++) any = any || P.gwid[c] == 3;
     for (int c = 0; aggs && c < kFastMaxA; c++) any = any || P.awid[c] == 3;

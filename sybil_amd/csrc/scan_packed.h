@@ -574,11 +574,17 @@ struct DynCursor {
 // FW: the filter columns' offsets come from one filter word per row (FastPlan::fword, fword.h) -- ONE full 16-byte load per lane
 // and tile into rf.v[0] where the columns take NF, and a bit-field extract per column and row where they take a width decode.
 // A property of the kernel like LEANV and DYN (the launcher picks it from P.fword): nothing in the loop asks which it is.
-template <int NF, int NG, int NA, int MODE, bool TIME, bool G1, int LEANV, bool FW>
+// KW: the key columns' and aggregation 0's offsets come from one key word per row (FastPlan::kword, a filter word in layout) --
+// ONE full 16-byte load per lane and tile into ra.v[0] where they take NG + 1, and a bit-field extract per field and row.
+// Likewise a property of the kernel (the launcher picks it from P.kword).
+template <int NF, int NG, int NA, int MODE, bool TIME, bool G1, int LEANV, bool FW, bool KW>
 __device__ __forceinline__ void packed_scan_dyn(const FastPlan &P, int64_t *lds, const FastLds &L, const bool max32, uint32_t &matched,
                                                 uint32_t &overflow) {
     static_assert(!FW || NF >= kFwordMinFields, "a filter word holds at least two columns");
     static_assert(kFwordMaxFields == kFastMaxF, "one field per filter column of a FastPlan");
+    static_assert(!KW || (!TIME && !G1 && NF >= 1 && NG >= 1 && NA >= 1), "a key word holds the keys and aggregation 0 of the late loop");
+    static_assert(!KW || kPackedLate, "a key word is read by the late loop");
+    static_assert(!KW || NG + 1 <= kFwordMaxFields, "one field per key column and one for aggregation 0");
     __shared__ uint32_t ring[4];
     const uint32_t tid = threadIdx.x;
     const uint32_t wave_row = __builtin_amdgcn_readfirstlane((tid & ~63u) * kPackedRows);  // the wave's first row inside a tile
@@ -628,17 +634,32 @@ __device__ __forceinline__ void packed_scan_dyn(const FastPlan &P, int64_t *lds,
     };
     auto issue_rest = [&](const DynTile &T, bool wanted) {
         if (TIME) issue(P.tcol, P.twid, T, wanted, rt.v[0], false);
+        if constexpr (KW) {
+            issue(P.kword, 4, T, wanted, ra.v[0], false);
+        } else {
 #pragma unroll
-        for (int c = 0; c < NG; c++) issue(P.gcol[c], G1 ? 1 : P.gwid[c], T, wanted, rg.v[c], G1);
+            for (int c = 0; c < NG; c++) issue(P.gcol[c], G1 ? 1 : P.gwid[c], T, wanted, rg.v[c], G1);
+        }
 #pragma unroll
-        for (int c = 0; c < NA; c++) issue(P.acol[c], P.awid[c], T, wanted, ra.v[c], false);
+        for (int c = KW ? 1 : 0; c < NA; c++) issue(P.acol[c], P.awid[c], T, wanted, ra.v[c], false);
     };
     auto decode_rest = [&]() {
         if (TIME) packed_decode(P.twid, rt.v[0], t.u[0]);
+        if constexpr (KW) {
+            const uint32_t wd[kPackedRows] = {ra.v[0].x, ra.v[0].y, ra.v[0].z, ra.v[0].w};
 #pragma unroll
-        for (int c = 0; c < NG; c++) packed_decode(G1 ? 1 : P.gwid[c], rg.v[c], g.u[c]);
+            for (int c = 0; c < NG; c++) {
 #pragma unroll
-        for (int c = 0; c < NA; c++) packed_decode(P.awid[c], ra.v[c], a.u[c]);
+                for (int k = 0; k < kPackedRows; k++) g.u[c][k] = __builtin_amdgcn_ubfe(wd[k], (uint32_t)P.gshift[c], (uint32_t)P.gbits[c]);
+            }
+#pragma unroll
+            for (int k = 0; k < kPackedRows; k++) a.u[0][k] = __builtin_amdgcn_ubfe(wd[k], (uint32_t)P.kashift, (uint32_t)P.kabits);
+        } else {
+#pragma unroll
+            for (int c = 0; c < NG; c++) packed_decode(G1 ? 1 : P.gwid[c], rg.v[c], g.u[c]);
+        }
+#pragma unroll
+        for (int c = KW ? 1 : 0; c < NA; c++) packed_decode(P.awid[c], ra.v[c], a.u[c]);
     };
     auto lane_left = [&](const DynTile &T) -> uint32_t { return T.rows > tid * kPackedRows ? T.rows - tid * kPackedRows : 0u; };
     if (kPackedLate && NF > 0 && NG + NA + (TIME ? 1 : 0) > 0) {
@@ -709,11 +730,16 @@ __device__ __forceinline__ void packed_scan_dyn(const FastPlan &P, int64_t *lds,
 // cost the loop 20 more spilled scalar registers; DESIGN 3.6 has the same finding for two loops in one kernel.)
 // DYN: FastPlan::dyn, likewise a property of the kernel -- the dynamic loops instead of the static ones (packed_scan_dyn).
 // FW: the dynamic loops read a filter word in the filter columns' place (packed_scan_dyn).
-template <int NF, int NG, int NA, int MODE, bool TIME, bool G1, bool NUL, int RING = 0, int LEANV = 0, bool DYN = false, bool FW = false>
+// KW: the dynamic late loop reads a key word in the place of the key columns and aggregation 0 (packed_scan_dyn).  G1 only
+// shapes the key loads a key word replaces: the KW kernels are the G1 = false ones.
+template <int NF, int NG, int NA, int MODE, bool TIME, bool G1, bool NUL, int RING = 0, int LEANV = 0, bool DYN = false, bool FW = false,
+          bool KW = false>
 __global__ __launch_bounds__(kWgThreads, SYBL_PACKED_WAVES_PER_EU) void k_scan_packed(const FastPlan P) {
     static_assert(LEANV == 0 || !NUL, "the NUL kernels mix row bodies: no proofs");
     static_assert(!DYN || (!NUL && RING == 0), "dynamic dealing is the plain kernels'");
     static_assert(!FW || (DYN && NF >= kFwordMinFields), "filter words are the dynamic loops', for two filter columns and more");
+    static_assert(!KW || (DYN && !TIME && !G1 && NG >= 1 && NA >= 1 && FW == (NF >= kFwordMinFields) && NF >= 1),
+                  "key words are the dynamic late loop's: keys and an aggregation, one filter column or a filter word");
     static_assert(!(LEANV & kLeanMoments) || (MODE == kFastMoments && NA >= 1), "the lean layout is moments mode's");
     static_assert(!(LEANV & kLeanProved) || MODE == kFastMoments || MODE == kFastHist, "the proved bodies are the bucket modes'");
     extern __shared__ int64_t lds[];
@@ -725,7 +751,7 @@ __global__ __launch_bounds__(kWgThreads, SYBL_PACKED_WAVES_PER_EU) void k_scan_p
 
     uint32_t matched = 0, overflow = 0;
     const uint64_t clock_in = P.wg_clock ? wall_clock64() : 0;  // (SYBL_WG_CLOCKS=1: when this workgroup's loop began and ended)
-    if constexpr (DYN) packed_scan_dyn<NF, NG, NA, MODE, TIME, G1, LEANV, FW>(P, lds, L, kMax32 && !P.ext_general, matched, overflow);
+    if constexpr (DYN) packed_scan_dyn<NF, NG, NA, MODE, TIME, G1, LEANV, FW, KW>(P, lds, L, kMax32 && !P.ext_general, matched, overflow);
     // (DYN: no segments -- the static loops below compile to nothing)
     const int s0 = DYN ? 0 : P.wg_seg_begin[blockIdx.x], s1 = DYN ? 0 : P.wg_seg_begin[blockIdx.x + 1];
     for (int si = s0; si < s1; si++) {
@@ -1376,24 +1402,24 @@ static hipError_t emit_packed_launch_nf(const EmitPlan &E, int ng, int na, int n
 }
 
 // the dynamic kernels (FastPlan::dyn) of one shape: the instantiation for the plan's lean bits, reading the filter columns or,
-// FW, a filter word
-template <int NF, int NG, int NA, int MODE, bool TIME, bool G1, bool FW, class LAUNCH>
+// FW, a filter word; KW, the keys and aggregation 0 from a key word
+template <int NF, int NG, int NA, int MODE, bool TIME, bool G1, bool FW, bool KW, class LAUNCH>
 static hipError_t packed_launch_dyn(const FastPlan &P, LAUNCH &&launch_lean) {
     if constexpr (NA >= 1 && MODE == kFastMoments) {
         switch (P.lean) {
-        case 0: return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, false, 0, 0, true, FW>);
-        case kLeanMoments: return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, false, 0, kLeanMoments, true, FW>);
-        case kLeanProved: return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, false, 0, kLeanProved, true, FW>);
-        case kLeanMoments | kLeanProved: return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, false, 0, kLeanMoments | kLeanProved, true, FW>);
+        case 0: return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, false, 0, 0, true, FW, KW>);
+        case kLeanMoments: return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, false, 0, kLeanMoments, true, FW, KW>);
+        case kLeanProved: return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, false, 0, kLeanProved, true, FW, KW>);
+        case kLeanMoments | kLeanProved: return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, false, 0, kLeanMoments | kLeanProved, true, FW, KW>);
         default: return hipErrorInvalidValue;
         }
     } else if constexpr (NA >= 1 && MODE == kFastHist) {
-        if (P.lean == kLeanProved) return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, false, 0, kLeanProved, true, FW>);
+        if (P.lean == kLeanProved) return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, false, 0, kLeanProved, true, FW, KW>);
         if (P.lean) return hipErrorInvalidValue;
-        return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, false, 0, 0, true, FW>);
+        return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, false, 0, 0, true, FW, KW>);
     } else {
         if (P.lean) return hipErrorInvalidValue;
-        return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, false, 0, 0, true, FW>);
+        return launch_lean(k_scan_packed<NF, NG, NA, MODE, TIME, G1, false, 0, 0, true, FW, KW>);
     }
 }
 
@@ -1419,17 +1445,32 @@ static hipError_t packed_launch_k1(const FastPlan &P, int n_wg, size_t lds_bytes
                 if constexpr (NF >= kFwordMinFields) {
                     for (int c = 0; c < NF; c++)
                         if (P.fbits[c] < 1 || P.fshift[c] < 0 || P.fshift[c] + P.fbits[c] > kFwordBits) return hipErrorInvalidValue;
-                    return packed_launch_dyn<NF, NG, NA, MODE, TIME, G1, true>(P, launch_lean);
                 } else {
                     return hipErrorInvalidValue;
                 }
             }
-            return packed_launch_dyn<NF, NG, NA, MODE, TIME, G1, false>(P, launch_lean);
+            // FastPlan::kword: the KW kernels -- the late loop without a time column, with a filter word iff NF >= 2 (what the
+            // planner takes a key word for, plan_kword); the fields must lie inside the word
+            if (P.kword) {
+                if constexpr (kPackedLate && !TIME && NF >= 1 && NG >= 1 && NA >= 1) {
+                    if ((P.fword != nullptr) != (NF >= kFwordMinFields)) return hipErrorInvalidValue;
+                    for (int c = 0; c < NG; c++)
+                        if (P.gbits[c] < 1 || P.gshift[c] < 0 || P.gshift[c] + P.gbits[c] > kFwordBits) return hipErrorInvalidValue;
+                    if (P.kabits < 1 || P.kashift < 0 || P.kashift + P.kabits > kFwordBits) return hipErrorInvalidValue;
+                    return packed_launch_dyn<NF, NG, NA, MODE, TIME, false, (NF >= kFwordMinFields), true>(P, launch_lean);
+                } else {
+                    return hipErrorInvalidValue;
+                }
+            }
+            if constexpr (NF >= kFwordMinFields) {
+                if (P.fword) return packed_launch_dyn<NF, NG, NA, MODE, TIME, G1, true, false>(P, launch_lean);
+            }
+            return packed_launch_dyn<NF, NG, NA, MODE, TIME, G1, false, false>(P, launch_lean);
         } else {
             return hipErrorInvalidValue;
         }
     }
-    if (P.fword) return hipErrorInvalidValue;  // (a filter word is read by the dynamic loops alone)
+    if (P.fword || P.kword) return hipErrorInvalidValue;  // (a filter word or a key word is read by the dynamic loops alone)
     // FastPlan::lean: the kernel must be the one the planner sized the table for.  (The lean kernels have no ring variants:
     // SYBL_PACKED_RING acts on a plan without lean -- set SYBL_NO_LEAN=1 beside it.)
     if (P.lean) {

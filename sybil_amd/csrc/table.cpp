@@ -898,27 +898,55 @@ static std::string fword_list(const Table *t, const FilterWord &w, bool names) {
 // SYBL_FWORD_MAX (default 2): the words a table holds; the least recently planned one goes first.
 // SYBL_PLAN_TRACE=1: `filter word: cols=c04,c05,c06 bits=10,10,10 rows=.. converted=.. bytes=..` when rows were converted,
 // `filter word: cols=.. freed` when a word goes.
-std::shared_ptr<FilterWord> table_build_fword(Table *t, const int *cols_in, int n) {
+//
+// Key words (Table::kwords; planner.cpp: plan_kword) are filter words in layout and life cycle -- the same pass, the same rules
+// of extension, rebuild and eviction -- over a plan's key columns and its aggregation 0 (`agg`, a table column index; -1 = a
+// filter word).  They are kept apart from the filter words in everything a caller can see: a list and a cap of their own
+// (SYBL_KWORD_MAX, default 2), their own size gate and off switch (SYBL_KWORD_MIN_ROWS, default 2^25 physical rows;
+// SYBL_NO_KWORD=1), and trace lines that begin `key word:`.  A key word is keyed by its set of columns AND by which of them is
+// the aggregation, because the bytes it must save depend on that: the columns cost today their stored widths, a 4-byte
+// aggregation that has or can get a narrow twin counted at 3 (word_bytes_today).
+struct WordKind {
+    std::vector<std::shared_ptr<FilterWord>> Table::*list;
+    const char *label, *env_min_rows, *env_max, *env_off;
+};
+static const WordKind kFilterWords = {&Table::fwords, "filter word", "SYBL_FWORD_MIN_ROWS", "SYBL_FWORD_MAX", "SYBL_NO_FWORD"};
+static const WordKind kKeyWords = {&Table::kwords, "key word", "SYBL_KWORD_MIN_ROWS", "SYBL_KWORD_MAX", "SYBL_NO_KWORD"};
+
+static std::shared_ptr<FilterWord> table_build_word(Table *t, const int *cols_in, int n, int agg, const WordKind &K);
+
+std::shared_ptr<FilterWord> table_build_fword(Table *t, const int *cols, int n) { return table_build_word(t, cols, n, -1, kFilterWords); }
+
+std::shared_ptr<FilterWord> table_build_kword(Table *t, const int *keys, int n_keys, int agg) {
+    if (n_keys < 1 || n_keys + 1 > kFwordMaxFields || agg < 0) return nullptr;
+    int cols[kFwordMaxFields];
+    for (int i = 0; i < n_keys; i++) cols[i] = keys[i];
+    cols[n_keys] = agg;
+    return table_build_word(t, cols, n_keys + 1, agg, kKeyWords);
+}
+
+static std::shared_ptr<FilterWord> table_build_word(Table *t, const int *cols_in, int n, int agg, const WordKind &K) {
+    std::vector<std::shared_ptr<FilterWord>> &words = t->*(K.list);
     if (n < kFwordMinFields || n > kFwordMaxFields) return nullptr;
     std::vector<int> cols(cols_in, cols_in + n);
     std::sort(cols.begin(), cols.end());  // the key is the SET: the same filters in another order reuse the word
     if (std::adjacent_find(cols.begin(), cols.end()) != cols.end() || cols.front() < 0 || cols.back() >= (int)t->cols.size()) return nullptr;
     int64_t min_rows = (int64_t)1 << 25, max_words = 2;
-    if (const char *e = env("SYBL_FWORD_MIN_ROWS")) min_rows = std::max<int64_t>(atoll(e), 1);
-    if (const char *e = env("SYBL_FWORD_MAX")) max_words = std::max<int64_t>(atoll(e), 1);
+    if (const char *e = env(K.env_min_rows)) min_rows = std::max<int64_t>(atoll(e), 1);
+    if (const char *e = env(K.env_max)) max_words = std::max<int64_t>(atoll(e), 1);
     const bool trace = env("SYBL_PLAN_TRACE") != nullptr;
-    auto held = [&]() { return std::find_if(t->fwords.begin(), t->fwords.end(), [&](const std::shared_ptr<FilterWord> &w) { return w->cols == cols; }); };
+    auto held = [&]() { return std::find_if(words.begin(), words.end(), [&](const std::shared_ptr<FilterWord> &w) { return w->cols == cols && w->agg == agg; }); };
     auto drop = [&](bool say) {  // the table's share goes; a prepared query that reads the word keeps its own
         auto it = held();
-        if (it == t->fwords.end()) return;
-        if (say && trace) fprintf(stderr, "filter word: cols=%s freed\n", fword_list(t, **it, true).c_str());
-        t->fwords.erase(it);
+        if (it == words.end()) return;
+        if (say && trace) fprintf(stderr, "%s: cols=%s freed\n", K.label, fword_list(t, **it, true).c_str());
+        words.erase(it);
     };
     auto it = held();
-    const bool current = it != t->fwords.end() && (*it)->version == t->version;
-    if (env("SYBL_NO_FWORD") || t->phys_rows < min_rows) {
+    const bool current = it != words.end() && (*it)->version == t->version;
+    if (env(K.env_off) || t->phys_rows < min_rows) {
         // (a word of this version may be what another prepared query scans: it stays, this plan just does not read it)
-        if (it != t->fwords.end() && !current) drop(false);
+        if (it != words.end() && !current) drop(false);
         return nullptr;
     }
     if (current) {
@@ -937,7 +965,7 @@ std::shared_ptr<FilterWord> table_build_fword(Table *t, const int *cols_in, int 
                    !c->has_missing && (unsigned __int128)((__int128)c->exact_max - (__int128)c->vbase) <= (unsigned __int128)UINT32_MAX;
         if (!eligible) break;
         max_off[i] = (uint32_t)((uint64_t)c->exact_max - (uint64_t)c->vbase);
-        widths += c->elem;
+        widths += word_bytes_today(c->elem, max_off[i], cols[(size_t)i] == agg);
     }
     // (a word must save bytes: two 2-byte columns are as well read as they are)
     eligible = eligible && fword_layout(max_off, n, bits, shift) <= kFwordBits && widths >= 5;
@@ -950,7 +978,7 @@ std::shared_ptr<FilterWord> table_build_fword(Table *t, const int *cols_in, int 
     // rows beyond them are packed, into the RECORDED fields.  Another width or base of a column, or anything else: the word is
     // built again from the first row.  Extrema that no longer fit the recorded fields: the word is freed and this plan reads the
     // columns (while the columns still fit 32 bits in all, the next prepare builds a word with the fields they need now).
-    std::shared_ptr<FilterWord> w = it != t->fwords.end() ? *it : nullptr;
+    std::shared_ptr<FilterWord> w = it != words.end() ? *it : nullptr;
     int64_t from = 0;
     if (w) {
         bool same = true, fits = true;
@@ -979,6 +1007,7 @@ std::shared_ptr<FilterWord> table_build_fword(Table *t, const int *cols_in, int 
         // a new array in a new word: a prepared query that still holds the old one keeps scanning the old array
         auto nw = std::make_shared<FilterWord>();
         nw->cols = cols;
+        nw->agg = agg;
         nw->n = n;
         for (int i = 0; i < n; i++) {
             const Column *c = t->cols[(size_t)cols[(size_t)i]].get();
@@ -988,11 +1017,11 @@ std::shared_ptr<FilterWord> table_build_fword(Table *t, const int *cols_in, int 
             nw->vbase[i] = c->vbase;
         }
         if (!w)
-            while ((int64_t)t->fwords.size() >= max_words) {  // bounded HBM: the least recently planned word makes room
-                auto lru = std::min_element(t->fwords.begin(), t->fwords.end(),
+            while ((int64_t)words.size() >= max_words) {  // bounded HBM: the least recently planned word makes room
+                auto lru = std::min_element(words.begin(), words.end(),
                                             [](const std::shared_ptr<FilterWord> &a, const std::shared_ptr<FilterWord> &b) { return a->planned < b->planned; });
-                if (trace) fprintf(stderr, "filter word: cols=%s freed\n", fword_list(t, **lru, true).c_str());
-                t->fwords.erase(lru);
+                if (trace) fprintf(stderr, "%s: cols=%s freed\n", K.label, fword_list(t, **lru, true).c_str());
+                words.erase(lru);
             }
         const int64_t cap = w ? std::max(need, w->cap_rows + w->cap_rows / 2) : need;
         if (hipMalloc(&nw->d_data, (size_t)cap * 4) != hipSuccess) {
@@ -1004,7 +1033,7 @@ std::shared_ptr<FilterWord> table_build_fword(Table *t, const int *cols_in, int 
             if (hipMemcpyAsync(nw->d_data, w->d_data, (size_t)from * 4, hipMemcpyDeviceToDevice, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return give_up();
         }
         if (w) drop(false);
-        t->fwords.push_back(nw);
+        words.push_back(nw);
         w = nw;
     }
     FwordPack S;
@@ -1021,7 +1050,7 @@ std::shared_ptr<FilterWord> table_build_fword(Table *t, const int *cols_in, int 
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) return give_up();
     if (trace)
-        fprintf(stderr, "filter word: cols=%s bits=%s rows=%lld converted=%lld bytes=%lld\n", fword_list(t, *w, true).c_str(), fword_list(t, *w, false).c_str(),
+        fprintf(stderr, "%s: cols=%s bits=%s rows=%lld converted=%lld bytes=%lld\n", K.label, fword_list(t, *w, true).c_str(), fword_list(t, *w, false).c_str(),
                 (long long)t->phys_rows, (long long)(t->phys_rows - from), (long long)(w->cap_rows * 4));
     w->rows = t->phys_rows;
     w->version = t->version;
@@ -1227,6 +1256,7 @@ int64_t sybl_table_hbm_bytes(const sybl_table *t) {
         if (c->narrow) b += c->narrow->cap_rows * c->narrow->elem;  // ... a 4-byte column's narrow twin
     }
     for (auto &w : t->fwords) b += w->cap_rows * 4;  // the filter words the table holds (one a query alone still holds is that query's)
+    for (auto &w : t->kwords) b += w->cap_rows * 4;  // the key words, likewise
     return b;
 }
 

@@ -9,6 +9,8 @@
 // run in turns against the 16 B mix and print min / median / max, so the two ranges can be set side by side.
 // Last, the 14 B mix against two 12 B mixes (k_loads_fword), in turns again: the three 2-byte filter columns as one 4-byte
 // "filter word" column (five loads per tile), and that with the two 1-byte key columns as one 2-byte column besides (four).
+// And the 12 B filter-word mix against an 11 B mix (V = 3): the two keys and the first aggregation as one 4-byte "key word"
+// beside the filter word and the second aggregation's 3-byte twin, three loads per tile, all dwordx4.
 // build: hipcc --offload-arch=gfx950 -O3 -o loadpat loadpat.hip ; run: ./loadpat [rows]
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -87,7 +89,9 @@ __global__ __launch_bounds__(kThreads) void k_loads_narrow(Cols C, int64_t rows,
 }
 
 // The 14 B mix (V = 0) against 12 B mixes: V = 1 reads one 4-byte column for the three 2-byte ones (a full dwordx4, 5 loads per
-// tile); V = 2 also reads one 2-byte column (a dwordx2) for the two 1-byte ones (4 loads per tile).  X holds those two columns.
+// tile); V = 2 also reads one 2-byte column (a dwordx2) for the two 1-byte ones (4 loads per tile); V = 3 reads the filter word,
+// one 4-byte key word (X.c[2]) for the two 1-byte keys and the first 3-byte twin, and the second twin: 11 B/row, 3 loads per
+// tile.  X holds the filter word, the key pair and the key word.
 template <int V>
 __global__ __launch_bounds__(kThreads) void k_loads_fword(Cols C, Cols X, int64_t rows, uint32_t *out) {
     const int64_t per_wg = (rows / gridDim.x) / (kThreads * 4) * (kThreads * 4);
@@ -103,9 +107,10 @@ __global__ __launch_bounds__(kThreads) void k_loads_fword(Cols C, Cols X, int64_
         if (V <= 1) {
 #pragma unroll
             for (int c = 3; c < 5; c++) acc ^= load_lane<4>(C.c[c] + wave_row, 256u, lane * 4);
-        } else acc ^= load_lane<8>(X.c[1] + wave_row * 2, 512u, lane * 8);
+        } else if (V == 2) acc ^= load_lane<8>(X.c[1] + wave_row * 2, 512u, lane * 8);
+        else acc ^= load_lane<16>(X.c[2] + wave_row * 4, 1024u, lane * 16);
 #pragma unroll
-        for (int c = 5; c < 7; c++) acc ^= load_lane<16>(C.c[c] + wave_row * 3, 768u, lane * 12);
+        for (int c = V == 3 ? 6 : 5; c < 7; c++) acc ^= load_lane<16>(C.c[c] + wave_row * 3, 768u, lane * 12);
     }
     if (acc == 0x12345678u) out[0] = acc;
 }
@@ -122,8 +127,8 @@ int main(int argc, char **argv) {
         C.c[c] = (const uint8_t *)p;
     }
     Cols X = {};
-    const int xwidths[2] = {4, 2};  // the filter word and the key pair of k_loads_fword
-    for (int c = 0; c < 2; c++) {
+    const int xwidths[3] = {4, 2, 4};  // the filter word, the key pair and the key word of k_loads_fword
+    for (int c = 0; c < 3; c++) {
         X.w[c] = xwidths[c];
         void *p;
         if (hipMalloc(&p, (size_t)rows * xwidths[c] + 4096) != hipSuccess) { printf("alloc failed\n"); return 1; }
@@ -200,6 +205,30 @@ int main(int argc, char **argv) {
                 for (int j = i + 1; j < kTurns - 1; j++)
                     if (m[j] < m[i]) { float t = m[i]; m[i] = m[j]; m[j] = t; }
             const double b = v == 0 ? 14.0 : 12.0;
+            printf("%-34s wgs %4d  min %.3f  med %.3f  max %.3f ms  %.0f GB/s of %.0f B/row at the median\n", names[v], wgs, m[0],
+                   m[(kTurns - 1) / 2], m[kTurns - 2], rows * b / (m[(kTurns - 1) / 2] * 1e-3) / 1e9, b);
+        }
+    }
+    // the 12 B filter-word mix against the 11 B mix with a key word, in turns as above
+    for (int wgs : {256, 512}) {
+        const int kTurns = 11;
+        float ms[2][kTurns];
+        for (int it = 0; it < kTurns; it++)
+            for (int v = 0; v < 2; v++) {
+                hipEventRecord(e0);
+                if (v == 0) hipLaunchKernelGGL((k_loads_fword<1>), dim3(wgs), dim3(kThreads), 0, 0, C, X, rows, out);
+                if (v == 1) hipLaunchKernelGGL((k_loads_fword<3>), dim3(wgs), dim3(kThreads), 0, 0, C, X, rows, out);
+                hipEventRecord(e1);
+                hipEventSynchronize(e1);
+                hipEventElapsedTime(&ms[v][it], e0, e1);
+            }
+        const char *names[2] = {"12 B mix (filter word)", "11 B mix (filter word, key word)"};
+        for (int v = 0; v < 2; v++) {
+            float *m = ms[v] + 1;
+            for (int i = 0; i < kTurns - 1; i++)
+                for (int j = i + 1; j < kTurns - 1; j++)
+                    if (m[j] < m[i]) { float t = m[i]; m[i] = m[j]; m[j] = t; }
+            const double b = v == 0 ? 12.0 : 11.0;
             printf("%-34s wgs %4d  min %.3f  med %.3f  max %.3f ms  %.0f GB/s of %.0f B/row at the median\n", names[v], wgs, m[0],
                    m[(kTurns - 1) / 2], m[kTurns - 2], rows * b / (m[(kTurns - 1) / 2] * 1e-3) / 1e9, b);
         }
