@@ -14,6 +14,7 @@
 #include <algorithm>
 
 #include "engine.h"
+#include "udiv_magic.h"
 #include "hll.h"
 #include "re2lite.h"
 
@@ -126,7 +127,12 @@ static bool fill_packed(Table *t, Query *q, const std::vector<int> &slot_col, Fa
         FP.late = nf > 0 && pass < 0.005 ? 1 : 0;
         if (const char *e = env("SYBL_LATE_PATH")) FP.late = atoi(e) != 0;  // (A/B: 0 / 1 whatever the estimate)
     }
-    for (int c = 0; c < ng; c++) FP.gdoff[c] = (uint32_t)((uint64_t)FP.gbase[c] - (uint64_t)FP.gmin[c]);
+    // (FastPlan::kfold: the digits' offsets times their strides, for the PROVED bodies' index over the stored offsets)
+    FP.kfold = 0;
+    for (int c = 0; c < ng; c++) {
+        FP.gdoff[c] = (uint32_t)((uint64_t)FP.gbase[c] - (uint64_t)FP.gmin[c]);
+        FP.kfold += FP.gdoff[c] * (uint32_t)FP.gstride[c];
+    }
     for (int c = 0; c < na; c++) {
         // Info.Min <= v <= Info.Max*10 (hist_basic.go:104) as a range of offsets; only looked at when the
         // aggregation tracks its own count
@@ -144,6 +150,11 @@ static bool fill_packed(Table *t, Query *q, const std::vector<int> &slot_col, Fa
     for (int c = 0; c < na; c++) {
         FP.adoff[c] = (uint32_t)((uint64_t)FP.abase[c] - (uint64_t)FP.hmin[c]);
         FP.pinv_bucket[c] = FP.bucket_size[c] ? (1.0 / (double)FP.bucket_size[c]) * shave : 0.0;
+        // (the PROVED bodies' quotient, udiv_magic.h: zeros for a bucket size plan_lean proves nothing about)
+        const UdivMagic m = udiv_magic(FP.bucket_size[c]);
+        FP.qmul[c] = m.mul;
+        FP.qshift[c] = m.shift;
+        FP.qoff2[c] = FP.adoff[c] << 1;
     }
     if (q->time_mode) {
         const SlotDesc &ts = P.slot[P.time_slot];
@@ -1602,7 +1613,9 @@ struct Planner {
     // FastPlan::lean (scan_fast.h): what k_scan_packed's plain kernels may assume about the resident rows, proved from the
     // columns' EXACT extrema (never the declared bounds; a table that grows re-plans its queries, as for cshift).
     //  * kLeanProved (moments and full-histogram modes): every group digit lies inside [0, gcard) -- the table is not windowed,
-    //    so it covers every cell --, and every bucket numerator value - h.Min and every bucket size is below 2^24;
+    //    so it covers every cell --, every key's stored offset value - base is below 2^24 (the bodies multiply IT by the stride
+    //    in 24 bits and add FastPlan::kfold), and every bucket numerator value - h.Min and every bucket size is below 2^24 (the
+    //    range udiv_magic.h's quotient is exact on);
     //  * kLeanMoments (moments mode): the lean words hold what a (cell, replica) can receive.  The layout's word count decides
     //    the replica count, that decides the rows per replica, and those decide whether the layout fits; when it does not, the
     //    plan keeps the layout AND the replica count it had.
@@ -1626,16 +1639,25 @@ struct Planner {
             }
             const __int128 lo = (__int128)c->exact_min - (__int128)FP.gmin[g], hi = (__int128)c->exact_max - (__int128)FP.gmin[g];
             digits = lo >= 0 && hi < (__int128)FP.gcard[g];
+            // (a stored offset is value - base >= 0; one of 2^24 or more has no 24-bit product: no proof, the f64-free body is not taken)
+            if ((__int128)c->exact_max - (__int128)FP.gbase[g] >= ((__int128)1 << 24) || (uint32_t)FP.gstride[g] >= (1u << 24)) digits = false;
         }
         for (int a = 0; a < na; a++) {
             const Column *c = t->cols[(size_t)q->aggs[(size_t)a].col].get();
-            if (FP.bucket_size[a] >= (1u << 24)) mul24 = false;
+            if (FP.bucket_size[a] < 1 || FP.bucket_size[a] >= (1u << 24)) mul24 = false;
             if (c->n_pop > 0) {
                 const __int128 lo = (__int128)c->exact_min - (__int128)FP.hmin[a], hi = (__int128)c->exact_max - (__int128)FP.hmin[a];
                 if (lo < 0 || hi >= ((__int128)1 << 24)) mul24 = false;
             }
         }
         if (digits && mul24) FP.lean |= (int32_t)kLeanProved;
+        // SYBL_PLAN_TRACE=1: `quotient: a0 d=1000 mul=1099511628 shift=9 off2=0 a1 .. kfold=0` -- the constants a PROVED body runs on
+        if ((FP.lean & (int32_t)kLeanProved) && env("SYBL_PLAN_TRACE") && !quiet) {
+            fprintf(stderr, "quotient:");
+            for (int a = 0; a < na; a++)
+                fprintf(stderr, " a%d d=%u mul=%u shift=%u off2=%u", a, (unsigned)FP.bucket_size[a], (unsigned)FP.qmul[a], (unsigned)FP.qshift[a], (unsigned)FP.qoff2[a]);
+            fprintf(stderr, " kfold=%u\n", (unsigned)FP.kfold);
+        }
         if (q->fast_mode != kFastMoments) {
             if (env("SYBL_PLAN_TRACE") && !quiet) fprintf(stderr, "lean hist: proved=%d digits=%d mul24=%d\n", (FP.lean & (int32_t)kLeanProved) ? 1 : 0, (int)digits, (int)mul24);
             return;

@@ -138,6 +138,13 @@ struct FastPlan {
     // nullptr = the columns.  gcol / gwid / gbase and acol[0] / awid[0] / abase[0] stay the stored columns' values.
     const uint32_t *kword;
     int32_t gshift[kFastMaxG], gbits[kFastMaxG], kashift, kabits;
+    // k_scan_packed's PROVED row bodies (kLeanProved below; planner.cpp: fill_packed) -- no other body reads these:
+    //   bucket number = umulhi((u << 1) + qoff2, qmul) >> qshift: udiv_magic.h's exact quotient of u + adoff by bucket_size,
+    //     qoff2 = 2 * adoff (mod 2^32) -- three vector instructions where packed_udiv takes seven, two of them f64;
+    //   cell = sum of u_c * gstride[c] over the keys' stored offsets + kfold, kfold = sum of gdoff[c] * gstride[c] (mod 2^32):
+    //     the digits' offsets folded into one constant (the body subtracts FastLds::cell_base from it once, outside its loop).
+    uint32_t qmul[kFastMaxA], qshift[kFastMaxA], qoff2[kFastMaxA];
+    uint32_t kfold;
 };
 
 hipError_t launch_scan_fast(const FastPlan &P, int nf, int ng, int na, int mode, bool time, bool gen, int n_wg,
@@ -166,8 +173,11 @@ inline bool fast_plan_has_narrow(const FastPlan &P, bool aggs) {
 //   B_j           sum(b) of aggregations 2j (low dword) and 2j + 1 (high dword): the row adds the 64-bit value {b_even, b_odd}
 //   Q_c           sum(b^2) of aggregation c
 // fast_finish unfolds them replica by replica into the published fields (Count, sum(v) = sum(u) + Count * abase, sum(b), sum(b^2)).
-// kLeanProved: every group digit is inside [0, gcard) and every bucket numerator is below 2^24 (and so is the bucket size):
-//   the bodies drop the per-digit compares -- `lcell < ncell` stays -- and the quotient's correction multiplies in 24 bits.
+// kLeanProved: every group digit is inside [0, gcard), every key's STORED offset is below 2^24, and every bucket numerator is
+//   below 2^24 (and so is the bucket size).  The bodies drop the per-digit compares -- `lcell < ncell` stays --; the cell index
+//   is one 24-bit multiply(-add) per key over the stored offsets plus FastPlan::kfold (exact mod 2^32: offset and stride are
+//   both below 2^24, and the true index is below n_cells < 2^24); and the bucket number is udiv_magic.h's multiply-shift, exact
+//   for every numerator and bucket size below 2^24 -- the proof of the quotient is that header's, the condition is unchanged.
 constexpr uint32_t kLeanMoments = 1u, kLeanProved = 2u;
 constexpr int lean_sum_fields(int na) { return na + (na + 1) / 2 + na; }
 constexpr int lean_bits(unsigned __int128 x) {

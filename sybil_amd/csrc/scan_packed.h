@@ -248,14 +248,27 @@ __device__ __forceinline__ void packed_decode_all(const FastPlan &P0, const Pack
 
 // floor(n / d) for 32-bit n, d >= 1.  inv_lo is 1/d scaled down by (1 - 2^-40), so the product never
 // exceeds the true quotient and is at most 1 short of it: one one-sided correction step is exact.
-// M24 (kLeanProved): n and d are below 2^24, so q <= n is too and q * d <= n cannot wrap -- the correction's product is a
-// 24-bit multiply (full rate) instead of a 32-bit one.
-template <bool M24 = false>
 __device__ __forceinline__ uint32_t packed_udiv(uint32_t n, uint32_t d, double inv_lo) {
     uint32_t q = (uint32_t)((double)n * inv_lo);
-    if (n - (M24 ? __umul24(q, d) : q * d) >= d) q += 1;
+    if (n - q * d >= d) q += 1;
     return q;
 }
+
+// Aggregation c's bucket number of the stored offset u: (u + adoff) / bucket_size.  PROVED (kLeanProved: numerator and bucket
+// size below 2^24): udiv_magic.h's exact multiply-shift on the planner's constants -- a shift-add, a high multiply and a shift,
+// no f64 -- where packed_udiv converts, multiplies and converts in f64 and corrects once.
+template <bool PROVED>
+__device__ __forceinline__ uint32_t packed_bucket(const FastPlan &P, const int c, const uint32_t u) {
+    if (PROVED) return __umulhi((u << 1) + P.qoff2[c], P.qmul[c]) >> P.qshift[c];
+    return packed_udiv(u + P.adoff[c], P.bucket_size[c], P.pinv_bucket[c]);
+}
+
+// Wave-uniform operands of the PROVED and lean row bodies that a loop may hold in VECTOR registers of its own (packed_scan_dyn:
+// a VOP3 instruction of gfx950 takes one scalar operand, so a second uniform one is otherwise moved into a vector register in
+// front of every use).  kfold: FastPlan::kfold - FastLds::cell_base; chi / zero: the high halves of the lean body's addends.
+struct PackedRowRegs {
+    uint32_t kfold, chi, zero;
+};
 
 // (OUT: the plain body with the outlier test -- a value beyond the last bucket is clipped and remembered, hist_basic.go:132-135:
 // what a fully populated tile of a NUL kernel runs when outliers are the only thing its plan asks of the NUL body)
@@ -268,7 +281,8 @@ template <int NF, int NG, int NA, int MODE, bool TIME, bool NUL, bool FRESH = fa
           bool PROVED = false, bool COUNTED = false, bool DERIVED = false>
 __device__ __forceinline__ void packed_row(const FastPlan &P0, const PackedTile<NF> &f, const PackedTile<NG> &g,
                                            const PackedTile<NA> &a, const PackedTile<1> &t, const int r, bool pass, int64_t *lds,
-                                           const FastLds &L, uint32_t &matched, uint32_t &overflow, const uint32_t xpop = 0xFu) {
+                                           const FastLds &L, uint32_t &matched, uint32_t &overflow, const uint32_t xpop = 0xFu,
+                                           const PackedRowRegs *X = nullptr) {
     static_assert(!LEAN || (MODE == kFastMoments && !NUL && !OUT && NA >= 1), "the lean layout is the plain moments body's");
     static_assert(!PROVED || (!NUL && !OUT), "proofs cover fully populated rows");
     static_assert(!DERIVED || (!NUL && !OUT), "only a row that counts in exactly one place can have its overflow derived");
@@ -291,20 +305,22 @@ __device__ __forceinline__ void packed_row(const FastPlan &P0, const PackedTile<
         }
         pass = pass & ok;
     }
-    uint32_t cell = 0;
+    // (PROVED: the sum starts from the folded constant and runs over the stored offsets -- FastPlan::kfold; `cell` is then the
+    // position inside this workgroup's LDS table from the start)
+    uint32_t cell = PROVED ? (X ? X->kfold : plan_fresh<FRESH>(P0).kfold - L.cell_base) : 0u;
     bool inb = true;
 #pragma unroll
     for (int c = 0; c < NG; c++) {
         const FastPlan &P = plan_fresh<FRESH>(P0);
-        const uint32_t d = g.u[c][r] + P.gdoff[c];  // value - gmin
+        const uint32_t d = PROVED ? g.u[c][r] : g.u[c][r] + P.gdoff[c];  // value - gmin (PROVED: the stored offset)
         if (NUL) {
             // MISSING_VALUE key (aggregate.go:138): its own digit, or the digit of the value -1
             const bool p = (g.pop[c] >> r) & 1u;
             inb = inb & (p ? d < (uint32_t)P.gvalues[c] : P.gmissing[c] >= 0);
             cell += p ? __umul24(d, (uint32_t)P.gstride[c]) : (uint32_t)P.gmissing[c];
         } else {
-            // (PROVED: the column's exact extrema lie inside the declared range and the table is not windowed -- `lcell < ncell`
-            // below still keeps a wrong proof from ever writing outside the table)
+            // (PROVED: the column's exact extrema lie inside the declared range, its stored offsets are below 2^24 and the table
+            // is not windowed -- `lcell < ncell` below still keeps a wrong proof from ever writing outside the table)
             if (!PROVED) inb = inb & (d < P.gcard[c]);
             cell += __umul24(d, (uint32_t)P.gstride[c]);  // aggregate.go:125-143 as a direct-mapped index
         }
@@ -325,7 +341,7 @@ __device__ __forceinline__ void packed_row(const FastPlan &P0, const PackedTile<
         cell += __umul24(tb, (uint32_t)P.tb_stride);
     }
     const uint32_t ncell = L.tab_cells;
-    const uint32_t lcell = cell - L.cell_base;  // position inside this workgroup's LDS table
+    const uint32_t lcell = PROVED ? cell : cell - L.cell_base;  // position inside this workgroup's LDS table
     inb = inb & (lcell < ncell);
     if (!COUNTED) matched += pass ? 1u : 0u;  // aggregate.go:117
     if (!DERIVED) overflow += (live & !inb) ? 1u : 0u;
@@ -336,7 +352,7 @@ __device__ __forceinline__ void packed_row(const FastPlan &P0, const PackedTile<
         // S_0 takes {u, 1 << (cshift - 32)}, B_j takes {b_even, b_odd}
         // The words of a (cell, replica) are NEIGHBOURS here (scan_fast.h): one address per row, every atomic a constant offset.
         constexpr uint32_t kB = NA, kQ = NA + (NA + 1) / 2, kW = (uint32_t)lean_sum_fields(NA);
-        const uint32_t chi = 1u << ((uint32_t)P.cshift - 32u);
+        const uint32_t chi = X ? X->chi : 1u << ((uint32_t)P.cshift - 32u), zero = X ? X->zero : 0u;
         char *const lean_p = (char *)lds + __umul24((lcell << rs) + L.rep, kW * 8u);
         auto add = [&](uint32_t field, int64_t v) {
             __hip_atomic_fetch_add((int64_t *)(lean_p + field * 8u), v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -345,13 +361,13 @@ __device__ __forceinline__ void packed_row(const FastPlan &P0, const PackedTile<
 #pragma unroll
         for (int c = 0; c < NA; c++) {
             const uint32_t u = a.u[c][r];
-            add((uint32_t)c, (int64_t)(((uint64_t)(c == 0 ? chi : 0u) << 32) | u));  // sum of OFFSETS (c == 0: and Count++)
-            b[c] = packed_udiv<PROVED>(u + P.adoff[c], P.bucket_size[c], P.pinv_bucket[c]);
-            add(kQ + (uint32_t)c, (int64_t)(uint64_t)(uint32_t)__umul24(b[c], b[c]));
+            add((uint32_t)c, (int64_t)(((uint64_t)(c == 0 ? chi : zero) << 32) | u));  // sum of OFFSETS (c == 0: and Count++)
+            b[c] = packed_bucket<PROVED>(P, c, u);
+            add(kQ + (uint32_t)c, (int64_t)(((uint64_t)zero << 32) | (uint32_t)__umul24(b[c], b[c])));
         }
 #pragma unroll
         for (int j = 0; j < (NA + 1) / 2; j++)
-            add(kB + (uint32_t)j, (int64_t)(((uint64_t)(2 * j + 1 < NA ? b[2 * j + 1 < NA ? 2 * j + 1 : 0] : 0u) << 32) | b[2 * j]));
+            add(kB + (uint32_t)j, (int64_t)(((uint64_t)(2 * j + 1 < NA ? b[2 * j + 1 < NA ? 2 * j + 1 : 0] : zero) << 32) | b[2 * j]));
         return;
     }
     // byte address of the cell's Count word; every other field of the cell is a wave-uniform byte
@@ -409,7 +425,7 @@ __device__ __forceinline__ void packed_row(const FastPlan &P0, const PackedTile<
         if (MODE == kFastMoments || MODE == kFastHist) {
             // bucket_value := (value - h.Min) / BucketSize, hist_basic.go:130; the planner guarantees
             // 0 <= value - h.Min < 2^32 and that no value reaches len(Values)
-            uint32_t b = packed_udiv<PROVED>(u + P.adoff[c], P.bucket_size[c], P.pinv_bucket[c]);
+            uint32_t b = packed_bucket<PROVED>(P, c, u);
             if ((NUL || OUT) && b >= (uint32_t)P.n_values[c]) {
                 // Outlier (hist_basic.go:132-135; BucketSize = size / 1000 truncates, so the top of many a column's range
                 // lies beyond the last bucket): clipped into the last bucket AND remembered as exact n, sum(o), sum(o^2)
@@ -436,7 +452,7 @@ __device__ __forceinline__ void packed_row(const FastPlan &P0, const PackedTile<
                 __hip_atomic_fetch_add(L.hist32 + lcell * (uint32_t)P.hist_stride + (uint32_t)P.hist_agg_off[c] + b, 1u,
                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             } else {
-                __hip_atomic_fetch_add(P.sum_out + P.hist_off + (int64_t)cell * P.hist_stride + P.hist_agg_off[c] + b,
+                __hip_atomic_fetch_add(P.sum_out + P.hist_off + (int64_t)(PROVED ? cell + L.cell_base : cell) * P.hist_stride + P.hist_agg_off[c] + b,
                                        (int64_t)1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
@@ -449,7 +465,7 @@ __device__ __forceinline__ void packed_row(const FastPlan &P0, const PackedTile<
 template <int NF, int NG, int NA, int MODE, bool TIME, bool FRESH, bool COUNTED, int LEANV, class PASS>
 __device__ __forceinline__ void packed_plain_tile(const FastPlan &P, const PackedTile<NF> &f, const PackedTile<NG> &g, const PackedTile<NA> &a,
                                                   const PackedTile<1> &t, PASS pass, int64_t *lds, const FastLds &L, const bool max32,
-                                                  uint32_t &matched, uint32_t &overflow) {
+                                                  uint32_t &matched, uint32_t &overflow, const PackedRowRegs *X = nullptr) {
     constexpr bool kLean = (LEANV & kLeanMoments) != 0, kProved = (LEANV & kLeanProved) != 0;
     if (MODE == kFastAvgMax && max32) {
 #pragma unroll
@@ -458,7 +474,8 @@ __device__ __forceinline__ void packed_plain_tile(const FastPlan &P, const Packe
     } else {
 #pragma unroll
         for (int k = 0; k < kPackedRows; k++)
-            packed_row<NF, NG, NA, MODE, TIME, false, FRESH, false, false, kLean, kProved, COUNTED, true>(P, f, g, a, t, k, pass(k), lds, L, matched, overflow);
+            packed_row<NF, NG, NA, MODE, TIME, false, FRESH, false, false, kLean, kProved, COUNTED, true>(P, f, g, a, t, k, pass(k), lds, L, matched, overflow,
+                                                                                                          0xFu, X);
     }
 }
 
@@ -598,6 +615,35 @@ __device__ __forceinline__ void packed_scan_dyn(const FastPlan &P, int64_t *lds,
     PackedTile<NG> g;
     PackedTile<NA> a;
     PackedTile<1> t;
+    // Wave-uniform operands of the loops' vector instructions, held in vector registers of their own from here on: the field
+    // widths of the words (a v_bfe_u32 takes the shift as its one scalar operand; the width beside it would be moved into a
+    // vector register in front of every extract) and PackedRowRegs for the PROVED bodies.  The empty asm makes each an opaque
+    // vector value the compiler cannot re-materialise from its scalar source per use.  Only the kernels that read a word or
+    // hold a PROVED body carry them: every other instantiation is what it was.
+    auto pinned = [](uint32_t x) -> uint32_t {
+        asm volatile("" : "+v"(x));
+        return x;
+    };
+    uint32_t fbits_v[NF > 0 ? NF : 1] = {}, gbits_v[NG > 0 ? NG : 1] = {}, kabits_v = 0;
+    if constexpr (FW) {
+#pragma unroll
+        for (int c = 0; c < NF; c++) fbits_v[c] = pinned((uint32_t)P.fbits[c]);
+    }
+    if constexpr (KW) {
+#pragma unroll
+        for (int c = 0; c < NG; c++) gbits_v[c] = pinned((uint32_t)P.gbits[c]);
+        kabits_v = pinned((uint32_t)P.kabits);
+    }
+    constexpr bool kRowRegs = (LEANV & kLeanProved) != 0;
+    PackedRowRegs regs = {0, 0, 0};
+    if constexpr (kRowRegs) {
+        regs.kfold = pinned(P.kfold - L.cell_base);
+        if constexpr ((LEANV & kLeanMoments) != 0) {
+            regs.chi = pinned(1u << ((uint32_t)P.cshift - 32u));
+            regs.zero = pinned(0u);
+        }
+    }
+    const PackedRowRegs *const X = kRowRegs ? &regs : nullptr;
     // one column's four rows for this lane: whole lanes up to the tile's end, like packed_issue_ring (`wanted` false, wave-
     // uniform: a descriptor of zero records -- the range check answers without touching memory)
     auto issue = [&](const void *col, int width, const DynTile &T, bool wanted, pu32x4 &raw, bool one_dword) {
@@ -625,7 +671,7 @@ __device__ __forceinline__ void packed_scan_dyn(const FastPlan &P, int64_t *lds,
 #pragma unroll
             for (int c = 0; c < NF; c++) {
 #pragma unroll
-                for (int k = 0; k < kPackedRows; k++) f.u[c][k] = __builtin_amdgcn_ubfe(wd[k], (uint32_t)P.fshift[c], (uint32_t)P.fbits[c]);
+                for (int k = 0; k < kPackedRows; k++) f.u[c][k] = __builtin_amdgcn_ubfe(wd[k], (uint32_t)P.fshift[c], fbits_v[c]);
             }
         } else {
 #pragma unroll
@@ -650,10 +696,10 @@ __device__ __forceinline__ void packed_scan_dyn(const FastPlan &P, int64_t *lds,
 #pragma unroll
             for (int c = 0; c < NG; c++) {
 #pragma unroll
-                for (int k = 0; k < kPackedRows; k++) g.u[c][k] = __builtin_amdgcn_ubfe(wd[k], (uint32_t)P.gshift[c], (uint32_t)P.gbits[c]);
+                for (int k = 0; k < kPackedRows; k++) g.u[c][k] = __builtin_amdgcn_ubfe(wd[k], (uint32_t)P.gshift[c], gbits_v[c]);
             }
 #pragma unroll
-            for (int k = 0; k < kPackedRows; k++) a.u[0][k] = __builtin_amdgcn_ubfe(wd[k], (uint32_t)P.kashift, (uint32_t)P.kabits);
+            for (int k = 0; k < kPackedRows; k++) a.u[0][k] = __builtin_amdgcn_ubfe(wd[k], (uint32_t)P.kashift, kabits_v);
         } else {
 #pragma unroll
             for (int c = 0; c < NG; c++) packed_decode(G1 ? 1 : P.gwid[c], rg.v[c], g.u[c]);
@@ -699,7 +745,7 @@ __device__ __forceinline__ void packed_scan_dyn(const FastPlan &P, int64_t *lds,
             cur.draw_ahead();
             matched += (uint32_t)__builtin_popcount(bits);
             packed_plain_tile<0, NG, NA, MODE, TIME, false, true, LEANV>(P, f0, g, a, t, [&](int k) -> bool { return (bits >> k) & 1u; }, lds, L, max32,
-                                                                         matched, overflow);
+                                                                         matched, overflow, X);
             bits = next_bits;
             T0 = T1;
             T1 = T2;
@@ -721,7 +767,7 @@ __device__ __forceinline__ void packed_scan_dyn(const FastPlan &P, int64_t *lds,
         const uint32_t left = lane_left(T0);
         if (NF == 0) matched += left < (uint32_t)kPackedRows ? left : (uint32_t)kPackedRows;  // no filter: every row of the tile
         packed_plain_tile<NF, NG, NA, MODE, TIME, false, NF == 0, LEANV>(P, f, g, a, t, [&](int k) { return (uint32_t)k < left; }, lds, L, max32,
-                                                                        matched, overflow);
+                                                                        matched, overflow, X);
         T0 = T1;
     }
 }
