@@ -912,6 +912,85 @@ const char *sybl_debug_compute_program(const char *expr, int32_t n_cols, const c
 int sybl_debug_compute_eval(const char *expr, int32_t n_cols, const char *const *names, const int32_t *types, const int64_t *values,
                             const uint8_t *populated, int64_t n_rows, int64_t *out, uint8_t *out_populated);
 
+/* ------------------------------------------------------------------ rollup
+ * A group-by whose result is again a resident table: one row per group, aggregated on the GPU (csrc/rollup.hip), which the
+ * engine can scan, save, concat, look up and roll up like any other table -- pre-aggregation (an hourly rollup by host kept
+ * resident while the raw table is freed), two-level aggregation (a histogram over a per-user count), a materialised group-by
+ * as the small side of sybl_table_lookup.  The reference has no such call; the semantics are this library's.  Restated
+ * deterministically:
+ *   source rows: the logical rows of t's live blocks in resident order, N of them; dead blocks and padding contribute nothing.
+ *   matching: every filter is evaluated exactly as sybl_table_select evaluates it (ANDed, strict, an unpopulated value fails,
+ *     at most 8 distinct filter columns).  When the planner proves that nothing matches the output is the columns and no
+ *     blocks, and no kernel runs.  A filter column need not be a key or an aggregated column.
+ *   key: an optional time part, then the n_groups (0..4) group columns in the order named.  Group columns are INT or STR; a SET
+ *     column, an unknown name, a name given twice or more than 4 columns: SYBL_E_INVAL naming it.  time_bucket > 0 makes
+ *     time_col (NULL / "" = "time"; an INT column) part of the key: the bucket value is v / B * B with Go's truncating division
+ *     (aggregate.go:174, the key of the reference's TimeResults), so -1 and 1 both fall into bucket 0; a matching row whose
+ *     time column is unpopulated is dropped and counted (rows_no_time), as the reference's time series does.  time_bucket = 0:
+ *     no time part; time_bucket < 0: SYBL_E_INVAL.  An unpopulated group value is a group of its own (the MISSING digit of
+ *     the query path) whose output value is unpopulated.  STR keys are compared and ordered by dictionary id.  No key at all:
+ *     one row, or none when nothing matches.
+ *   aggregated columns: n_aggs (0..8) INT columns, each with a non-empty comma-separated subset of "n", "sum", "min", "max" in
+ *     `ops`; anything else: SYBL_E_INVAL.  Every group keeps count (its matching rows) and, per aggregated column, n (the
+ *     populated values), sum (the low 64 bits of the sum, as everywhere in the engine), min and max.  Unpopulated values
+ *     contribute nothing.
+ *   output rows: one per distinct key among the kept rows, G of them, ascending lexicographically by (bucket, group 1, ..), an
+ *     unpopulated value before every populated one.  The order does not depend on how workgroups were scheduled: two calls
+ *     give identical tables.  Output block j = rows [j * block_rows, min(G, (j+1) * block_rows)); block_rows as for select.
+ *   output columns, in this order: the time column, if bucketed (it keeps its name and holds bucket starts); the group columns
+ *     by digest's rules (same name, type and IntInfo, dictionary id for id, the source's (width, base) -- every value is a
+ *     source value --, a bitmap iff the MISSING group occurs); count_name (NULL / "" = "count"); per aggregated column, in the
+ *     order named, those asked for of <col>_n, <col>_sum, <col>_min, <col>_max.  count and _n are always populated; _sum,
+ *     _min and _max are unpopulated (stored 0) for a group with n = 0, and the column has a bitmap iff some group is so.  A
+ *     name that collides: SYBL_E_INVAL naming it.
+ *   storage of the new columns (time, count, aggregates): in compact mode by the storage rule over their exact output extrema
+ *     (width 1, base 0 without a populated value), otherwise canonical.  Per-block statistics are exact for every column.
+ *   limits: the mixed-radix composite key -- per key column the span of its tracked extrema (dictionary ids for STR, the
+ *     quotients lo / B .. hi / B for the time part), plus one where the column has a bitmap, the time part most significant --
+ *     must stay within 2^62: beyond, SYBL_E_INVAL saying so (a key column spanning the whole int64 range does that alone).  At
+ *     most 2^27 cells or hash slots; a hash table that fills: SYBL_E_NOMEM.  N is unlimited.
+ * The source is untouched and its version unmoved; the output owns everything and outlives it.  Rank-local, never collective
+ * (across ranks: sybl_table_concat of the ranks' rollups, then a rollup of the sums); runs on the ctx stream, is complete on
+ * return and thread-safe per ctx like select.  Any failure leaves *out NULL and sybl_last_error beginning
+ * "sybl_table_rollup: "; when HBM runs out: SYBL_E_NOMEM, everything freed.
+ * Out of scope: weights; histograms or percentiles per group; count distinct; SET keys; float averages (divide _sum by _n with
+ * sybl_table_compute). */
+typedef struct {
+    const char *col;   /* an INT column */
+    const char *ops;   /* e.g. "sum,max": a non-empty subset of n, sum, min, max */
+} sybl_rollup_agg;
+
+typedef struct {
+    int32_t n_filters;
+    const sybl_filter *filters;
+    int32_t n_groups;
+    const char *const *groups;
+    int32_t n_aggs;
+    const sybl_rollup_agg *aggs;
+    const char *time_col;     /* looked at when time_bucket > 0 */
+    int64_t time_bucket;
+    const char *count_name;
+    int32_t block_rows;       /* 0 = 65536 */
+} sybl_rollup_desc;
+
+int sybl_table_rollup(sybl_table *t, const sybl_rollup_desc *d, sybl_table **out);
+
+/* What the sybl_table_rollup that made this table did (zeros for any other table).  path: 1 = direct cells accumulated in
+ * LDS, 2 = direct cells in HBM, 3 = hash; 0 = no kernel ran. */
+typedef struct {
+    int64_t rows_in;          /* N */
+    int64_t rows_matched;     /* rows that passed the filters */
+    int64_t rows_no_time;     /* ... of them dropped: time column unpopulated */
+    int64_t groups;           /* G */
+    int64_t blocks_out;
+    int32_t path;
+    int32_t fields;           /* int64 fields per cell: 1 + 4 per aggregated column */
+    int64_t cells_or_slots;
+    double filter_ms, accumulate_ms, order_ms, emit_ms;                  /* hipEvent time of the phases */
+    int64_t filter_bytes, accumulate_bytes, order_bytes, emit_bytes;     /* computed from the shapes */
+} sybl_rollup_stats;
+int sybl_table_rollup_stats(const sybl_table *t, sybl_rollup_stats *out);
+
 /* Test hook (no GPU needed): the library's regular-expression engine for re / nre str filters -- Go regexp
  * (RE2) syntax, unanchored search like regexp.MatchString (filter.go:213-236).  1 = match, 0 = no match,
  * -1 = the pattern does not compile (sybl_last_error says why). */

@@ -187,6 +187,27 @@ class ComputeStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class RollupAgg(C.Structure):
+    _fields_ = [("col", C.c_char_p), ("ops", C.c_char_p)]
+
+
+class RollupDesc(C.Structure):
+    _fields_ = [("n_filters", C.c_int32), ("filters", C.POINTER(Filter)), ("n_groups", C.c_int32),
+                ("groups", C.POINTER(C.c_char_p)), ("n_aggs", C.c_int32), ("aggs", C.POINTER(RollupAgg)),
+                ("time_col", C.c_char_p), ("time_bucket", C.c_int64), ("count_name", C.c_char_p), ("block_rows", C.c_int32)]
+
+
+class RollupStats(C.Structure):
+    _fields_ = [("rows_in", C.c_int64), ("rows_matched", C.c_int64), ("rows_no_time", C.c_int64), ("groups", C.c_int64),
+                ("blocks_out", C.c_int64), ("path", C.c_int32), ("fields", C.c_int32), ("cells_or_slots", C.c_int64),
+                ("filter_ms", C.c_double), ("accumulate_ms", C.c_double), ("order_ms", C.c_double), ("emit_ms", C.c_double),
+                ("filter_bytes", C.c_int64), ("accumulate_bytes", C.c_int64), ("order_bytes", C.c_int64),
+                ("emit_bytes", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol include/sybilgpu.h declares: (restype, argtypes)
 P = C.c_void_p
 SIGNATURES = {
@@ -275,6 +296,8 @@ SIGNATURES = {
     "sybl_table_lookup_stats": (C.c_int, [P, C.POINTER(LookupStats)]),
     "sybl_table_compute": (C.c_int, [P, C.POINTER(ComputeDesc), C.POINTER(P)]),
     "sybl_table_compute_stats": (C.c_int, [P, C.POINTER(ComputeStats)]),
+    "sybl_table_rollup": (C.c_int, [P, C.POINTER(RollupDesc), C.POINTER(P)]),
+    "sybl_table_rollup_stats": (C.c_int, [P, C.POINTER(RollupStats)]),
     "sybl_debug_compute_program": (C.c_char_p, [C.c_char_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]),
     "sybl_debug_compute_eval": (C.c_int, [C.c_char_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), P, P, C.c_int64, P, P]),
 }

@@ -245,6 +245,7 @@ struct Table {
     sybl_concat_stats concat_stats{};  // of the sybl_table_concat that made this table (concat.hip)
     sybl_lookup_stats lookup_stats{};  // of the sybl_table_lookup that made this table (lookup.hip)
     sybl_compute_stats compute_stats{};  // of the sybl_table_compute that made this table (compute.hip)
+    sybl_rollup_stats rollup_stats{};  // of the sybl_table_rollup that made this table (rollup.hip)
     std::string src_dir;           // <dir>/<table> the table was opened from ("" = built through the ABI)
     int src_rank = 0, src_nranks = 1;
     std::vector<LoadedBlock> loaded;
@@ -610,6 +611,7 @@ int select_run(Table *t, const sybl_select_desc *d, sybl_table **out);  // selec
 int concat_run(const sybl_concat_desc *d, sybl_table **out);  // concat.hip
 int lookup_run(Table *t, const sybl_lookup_desc *d, sybl_table **out);  // lookup.hip
 int compute_run(Table *t, const sybl_compute_desc *d, sybl_table **out);  // compute.hip
+int rollup_run(Table *t, const sybl_rollup_desc *d, sybl_table **out);  // rollup.hip
 int query_rescan_without_part_hist(Query *q);
 
 constexpr int kMaxScatterRanks = 64;  // the SUM section is padded so that a reduce-scatter over up to this many ranks fits in place

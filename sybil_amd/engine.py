@@ -387,6 +387,37 @@ class Table:
         N.check(N.lib().sybl_table_compute_stats(self._h, C.byref(st)))
         return st.as_dict()
 
+    def rollup(self, groups=(), aggs=(), filters=(), time_col=None, time_bucket=0, count_name="count", block_rows=0):
+        """A group-by as a NEW resident table (sybl_table_rollup): one row per distinct key among the rows that pass `filters`,
+        ascending by (time bucket, groups..), holding the key columns, `count_name` and, per aggregated column, those asked for
+        of <col>_n, <col>_sum, <col>_min, <col>_max.  groups: up to 4 int / str columns; aggs: a list of (column, "sum,min,max,n")
+        pairs, or a dict in insertion order; time_bucket > 0 makes time_col (None = "time") the first part of the key, cut
+        into buckets of that size.  This table is untouched; free both."""
+        keep = []
+        pairs = list(aggs.items()) if isinstance(aggs, dict) else [tuple(a) for a in aggs]
+        aarr = (N.RollupAgg * max(len(pairs), 1))()
+        for i, (col, ops) in enumerate(pairs):
+            aarr[i] = N.RollupAgg(_b(col), _b(ops) if ops is not None else None)
+        g = [_b(x) for x in groups]
+        garr = (C.c_char_p * max(len(g), 1))(*g)
+        d = N.RollupDesc()
+        d.n_filters, d.filters = len(filters), C.cast(self._filter_array(filters, keep), C.POINTER(N.Filter))
+        d.n_groups, d.groups = len(g), C.cast(garr, C.POINTER(C.c_char_p))
+        d.n_aggs, d.aggs = len(pairs), C.cast(aarr, C.POINTER(N.RollupAgg))
+        d.time_col = _b(time_col) if time_col is not None else None
+        d.time_bucket = time_bucket
+        d.count_name = _b(count_name) if count_name is not None else None
+        d.block_rows = block_rows
+        h = C.c_void_p()
+        N.check(N.lib().sybl_table_rollup(self._h, C.byref(d), C.byref(h)))
+        return Table(self.ctx, h, self.name)
+
+    def rollup_stats(self):
+        """Path, counts, device time and bytes of the phases of the rollup() that made this table (sybl_table_rollup_stats)."""
+        st = N.RollupStats()
+        N.check(N.lib().sybl_table_rollup_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
     def query(self, filters=(), groups=(), aggs=(), op="avg", hist_bucket=0, want_percentiles=True, time_col=None,
               time_bucket=0, weight_col=None, order_by="$COUNT", order_asc=False, limit=0, block_skip=False, loghist=False, str_replace=(),
               distincts=(), printed_only=False):
