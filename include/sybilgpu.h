@@ -934,15 +934,22 @@ int sybl_debug_compute_eval(const char *expr, int32_t n_cols, const char *const 
  *     `ops`; anything else: SYBL_E_INVAL.  Every group keeps count (its matching rows) and, per aggregated column, n (the
  *     populated values), sum (the low 64 bits of the sum, as everywhere in the engine), min and max.  Unpopulated values
  *     contribute nothing.
+ *   percentiles: `ops` also takes tokens p<k>, <k> a decimal integer 1..99 without a leading zero (so p0, p100, p05, p5.5 and p
+ *     are refused, as are a token given twice and more than 8 percentile tokens on one column: SYBL_E_INVAL quoting the ops); a
+ *     column may carry percentile tokens only ("p50").  With the group's n populated values of the column sorted ascending, p<k>
+ *     is the element of 1-based rank ceil(k * n / 100), computed as (k * n + 99) / 100: nearest rank, no interpolation, exact at
+ *     every int64 value.  n = 0: unpopulated, stored 0, exactly like _min / _max.  Filters, the time part, rows_no_time and the
+ *     MISSING group behave as for the other aggregates.  The values are sorted on the GPU (one sort per column, shared by its
+ *     percentiles; at most 2^31 - 1 values per column); sybl_table_rollup_pct_stats says how.
  *   output rows: one per distinct key among the kept rows, G of them, ascending lexicographically by (bucket, group 1, ..), an
  *     unpopulated value before every populated one.  The order does not depend on how workgroups were scheduled: two calls
  *     give identical tables.  Output block j = rows [j * block_rows, min(G, (j+1) * block_rows)); block_rows as for select.
  *   output columns, in this order: the time column, if bucketed (it keeps its name and holds bucket starts); the group columns
  *     by digest's rules (same name, type and IntInfo, dictionary id for id, the source's (width, base) -- every value is a
  *     source value --, a bitmap iff the MISSING group occurs); count_name (NULL / "" = "count"); per aggregated column, in the
- *     order named, those asked for of <col>_n, <col>_sum, <col>_min, <col>_max.  count and _n are always populated; _sum,
- *     _min and _max are unpopulated (stored 0) for a group with n = 0, and the column has a bitmap iff some group is so.  A
- *     name that collides: SYBL_E_INVAL naming it.
+ *     order named, those asked for of <col>_n, <col>_sum, <col>_min, <col>_max, then its <col>_p<k> in ascending k whatever
+ *     their order in `ops`.  count and _n are always populated; _sum, _min, _max and _p<k> are unpopulated (stored 0) for a
+ *     group with n = 0, and the column has a bitmap iff some group is so.  A name that collides: SYBL_E_INVAL naming it.
  *   storage of the new columns (time, count, aggregates): in compact mode by the storage rule over their exact output extrema
  *     (width 1, base 0 without a populated value), otherwise canonical.  Per-block statistics are exact for every column.
  *   limits: the mixed-radix composite key -- per key column the span of its tracked extrema (dictionary ids for STR, the
@@ -950,14 +957,16 @@ int sybl_debug_compute_eval(const char *expr, int32_t n_cols, const char *const 
  *     must stay within 2^62: beyond, SYBL_E_INVAL saying so (a key column spanning the whole int64 range does that alone).  At
  *     most 2^27 cells or hash slots; a hash table that fills: SYBL_E_NOMEM.  N is unlimited.
  * The source is untouched and its version unmoved; the output owns everything and outlives it.  Rank-local, never collective
- * (across ranks: sybl_table_concat of the ranks' rollups, then a rollup of the sums); runs on the ctx stream, is complete on
+ * (across ranks: sybl_table_concat of the ranks' rollups, then a rollup of the sums -- percentiles do NOT merge that way: concat
+ * the ranks' raw rows and roll those up); runs on the ctx stream, is complete on
  * return and thread-safe per ctx like select.  Any failure leaves *out NULL and sybl_last_error beginning
  * "sybl_table_rollup: "; when HBM runs out: SYBL_E_NOMEM, everything freed.
- * Out of scope: weights; histograms or percentiles per group; count distinct; SET keys; float averages (divide _sum by _n with
+ * Out of scope: weights; histograms per group; interpolated or approximate percentiles, percentiles of STR or SET columns;
+ * count distinct; SET keys; float averages (divide _sum by _n with
  * sybl_table_compute). */
 typedef struct {
     const char *col;   /* an INT column */
-    const char *ops;   /* e.g. "sum,max": a non-empty subset of n, sum, min, max */
+    const char *ops;   /* e.g. "sum,max,p50,p99": a non-empty subset of n, sum, min, max and up to 8 of p1 .. p99 */
 } sybl_rollup_agg;
 
 typedef struct {
@@ -990,6 +999,22 @@ typedef struct {
     int64_t filter_bytes, accumulate_bytes, order_bytes, emit_bytes;     /* computed from the shapes */
 } sybl_rollup_stats;
 int sybl_table_rollup_stats(const sybl_table *t, sybl_rollup_stats *out);
+
+/* What the percentiles of the sybl_table_rollup that made this table cost (zeros for any table that no percentile rollup
+ * made).  Per aggregated column with percentiles the populated values of the matching rows are sorted by cell << vbits |
+ * (v - lo): as uint32 keys where the bits of the cells and of the value span fit 32 (variant32), as uint64 keys where they fit
+ * 64 (variant64), otherwise by value and then stably by cell (variant_pairs).  A column none of whose values passed is not
+ * sorted and counts in no variant. */
+typedef struct {
+    int32_t columns;          /* aggregated columns with at least one percentile */
+    int32_t percentiles;      /* output columns made */
+    int32_t variant32, variant64, variant_pairs;   /* columns sorted by each variant */
+    int32_t key_bits_max;     /* the widest cell + value key */
+    int64_t items;            /* values sorted, summed over the columns */
+    double keys_ms, sort_ms, pick_ms;              /* hipEvent time, summed over the columns */
+    int64_t keys_bytes, sort_bytes, pick_bytes;    /* computed from the shapes */
+} sybl_rollup_pct_stats;
+int sybl_table_rollup_pct_stats(const sybl_table *t, sybl_rollup_pct_stats *out);
 
 /* Test hook (no GPU needed): the library's regular-expression engine for re / nre str filters -- Go regexp
  * (RE2) syntax, unanchored search like regexp.MatchString (filter.go:213-236).  1 = match, 0 = no match,

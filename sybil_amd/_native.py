@@ -208,6 +208,16 @@ class RollupStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class RollupPctStats(C.Structure):
+    _fields_ = [("columns", C.c_int32), ("percentiles", C.c_int32), ("variant32", C.c_int32), ("variant64", C.c_int32),
+                ("variant_pairs", C.c_int32), ("key_bits_max", C.c_int32), ("items", C.c_int64),
+                ("keys_ms", C.c_double), ("sort_ms", C.c_double), ("pick_ms", C.c_double),
+                ("keys_bytes", C.c_int64), ("sort_bytes", C.c_int64), ("pick_bytes", C.c_int64)]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # every symbol include/sybilgpu.h declares: (restype, argtypes)
 P = C.c_void_p
 SIGNATURES = {
@@ -298,6 +308,7 @@ SIGNATURES = {
     "sybl_table_compute_stats": (C.c_int, [P, C.POINTER(ComputeStats)]),
     "sybl_table_rollup": (C.c_int, [P, C.POINTER(RollupDesc), C.POINTER(P)]),
     "sybl_table_rollup_stats": (C.c_int, [P, C.POINTER(RollupStats)]),
+    "sybl_table_rollup_pct_stats": (C.c_int, [P, C.POINTER(RollupPctStats)]),
     "sybl_debug_compute_program": (C.c_char_p, [C.c_char_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32)]),
     "sybl_debug_compute_eval": (C.c_int, [C.c_char_p, C.c_int32, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), P, P, C.c_int64, P, P]),
 }

@@ -246,6 +246,7 @@ struct Table {
     sybl_lookup_stats lookup_stats{};  // of the sybl_table_lookup that made this table (lookup.hip)
     sybl_compute_stats compute_stats{};  // of the sybl_table_compute that made this table (compute.hip)
     sybl_rollup_stats rollup_stats{};  // of the sybl_table_rollup that made this table (rollup.hip)
+    sybl_rollup_pct_stats rollup_pct_stats{};  // ... and of its percentiles
     std::string src_dir;           // <dir>/<table> the table was opened from ("" = built through the ABI)
     int src_rank = 0, src_nranks = 1;
     std::vector<LoadedBlock> loaded;

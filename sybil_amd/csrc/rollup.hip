@@ -18,8 +18,16 @@
 //   order         direct: the occupied cells in cell order (hipcub::DeviceSelect::Flagged over count > 0: cell order is key
 //                 order, nothing is sorted).  hash: the claimed slots compacted likewise, their composites fetched, and
 //                 hipcub::DeviceRadixSort::SortPairs over exactly the composite's bits.  One readback brings G and the counters.
+//   percentiles   once per aggregated column with p<k> tokens, between order and emit, every column in the same pool buffers:
+//                 the exclusive sum of the column's n field over the cells (where each cell's values start); k_ru_pct_keys --
+//                 k_ru_accum's row front end, the cell found and never claimed -- writes one sort key cell << vbits | (v - lo)
+//                 per matching populated value, compacted with wave ballots and one cursor atomic per workgroup and tile;
+//                 hipcub::DeviceRadixSort over exactly the key's bits (uint32 keys, uint64 keys, or -- beyond 64 bits -- by value
+//                 with the cell as payload and then stably by cell: rollup_plan.h); k_ru_pct_pick takes the value of rank
+//                 (k * n + 99) / 100 for every (output row, percentile).  One sort serves all percentiles of a column.  The
+//                 item counts travel with the order phase's readback: no further wait.
 //   k_ru_emit     a lane owns four consecutive OUTPUT physical rows of one column: it decodes the composite into the column's
-//                 digit, or reads the cell's field.  <false, 0>: the range pass -- min / max / populated, one set of atomics per
+//                 digit, reads the cell's field, or reads an array by output row (a percentile).  <false, 0>: the range pass -- min / max / populated, one set of atomics per
 //                 workgroup --, read back once for all columns; the host fits (width, base) with the storage rule.  <true, W>:
 //                 the store pass -- (v - base) at width W as whole dwords, 0 in padding and where unpopulated; validity words
 //                 OR-ed together from the 8 lanes that hold a word's 32 rows.
@@ -161,6 +169,84 @@ __device__ __forceinline__ int64_t ru_wave_max(int64_t v) {
     return v;
 }
 
+// A composite's slot in a table that is complete: found, or -1 -- nothing is claimed.  The walk is bounded as above.
+__device__ __forceinline__ int32_t ru_find(const uint64_t *keys, uint32_t mask, uint64_t key) {
+    uint32_t h = (uint32_t)(splitmix64(key) >> 32) & mask;
+    const uint32_t limit = mask + 1u < kHashMaxProbes ? mask + 1u : kHashMaxProbes;
+    for (uint32_t probe = 0; probe < limit; probe++) {
+        const uint64_t k = keys[h];
+        if (k == key) return (int32_t)h;
+        if (k == kHashEmpty) return -1;
+        h = (h + 1) & mask;
+    }
+    return -1;
+}
+
+// The row front end of a tile, shared by k_ru_accum and k_ru_pct_keys: the lane's four rows p0 .. p0 + 3 of the tile's block, the
+// returned mask of those that are live, pass the filters and have a key (a row without a time value is dropped and counted),
+// and their cells -- the composite, or its slot: find-or-claim (<CLAIM>) or find-only.  *lost counts rows whose composite found
+// no slot; find-only also those whose composite is not below n_cells (cannot be; never an address).
+template <bool HASH, bool CLAIM>
+__device__ __forceinline__ uint32_t ru_rows(const RuArgs &A, int64_t tile, int tid, int64_t *p0_out, uint32_t cell[kRuRows], long long *matched,
+                                            long long *no_time, long long *lost) {
+    const RowBlk B = A.blk[block_of(A.blk, A.nb, tile, &RowBlk::base)];  // (uniform, scalar)
+    const int64_t p0 = B.start + (tile - B.base) * kRuTileRows + (int64_t)tid * kRuRows;
+    const int64_t left = B.start + B.n - p0;
+    uint32_t m = left <= 0 ? 0u : left >= kRuRows ? 0xFu : (1u << (int)left) - 1u;  // the lane's live rows ...
+    if (A.bits != nullptr && m != 0) m &= A.bits[p0 >> 5] >> (p0 & 31);               // ... that pass the filters
+    *matched += __popc(m);
+
+    // ---- the composite key
+    uint64_t comp[kRuRows] = {0, 0, 0, 0};
+    for (int g = 0; g < A.n_keys; g++) {
+        int64_t v[kRuRows];
+        const uint32_t pop = ru_load(A.keys[g], p0, m, v);
+        const int64_t lo = A.key_lo[g];
+        const uint64_t stride = A.key_stride[g];
+        if (g == 0 && A.has_time) {
+            *no_time += __popc(m & ~pop);
+            m &= pop;
+#pragma unroll
+            for (int k = 0; k < kRuRows; k++)
+                if ((m >> k) & 1u) comp[k] += (uint64_t)(v[k] / A.time_bucket - lo) * stride;
+        } else {
+            const uint64_t miss = (uint64_t)A.keys[g].missing;
+            if (!miss) m &= pop;  // (a column without a bitmap has every row populated)
+#pragma unroll
+            for (int k = 0; k < kRuRows; k++)
+                if ((pop >> k) & 1u) comp[k] += ((uint64_t)v[k] - (uint64_t)lo + miss) * stride;
+        }
+    }
+
+    // ---- the cell: the composite itself, or its slot; a lane's consecutive rows of one key probe once
+#pragma unroll
+    for (int k = 0; k < kRuRows; k++) cell[k] = 0;
+#pragma unroll
+    for (int k = 0; k < kRuRows; k++) {
+        if (!((m >> k) & 1u)) continue;
+        if (HASH) {
+            if (k > 0 && ((m >> (k - 1)) & 1u) && comp[k] == comp[k - 1]) {
+                cell[k] = cell[k - 1];
+                continue;
+            }
+            const int32_t s = CLAIM ? ru_find_or_claim(A.hkeys, A.hmask, comp[k]) : ru_find(A.hkeys, A.hmask, comp[k]);
+            if (s < 0) {
+                (*lost)++;
+                m &= ~(1u << k);
+            } else {
+                cell[k] = (uint32_t)s;
+            }
+        } else if (comp[k] >= (uint64_t)A.n_cells) {
+            m &= ~(1u << k);  // (beyond the tracked extrema: cannot be; never an address)
+            if (!CLAIM) (*lost)++;
+        } else {
+            cell[k] = (uint32_t)comp[k];
+        }
+    }
+    *p0_out = p0;
+    return m;
+}
+
 template <bool LDS, bool HASH>
 __global__ __launch_bounds__(kRuThreads) void k_ru_accum(const RuArgs A) {
     extern __shared__ int64_t ru_lds[];  // <LDS>: [fields][n_cells]
@@ -175,58 +261,9 @@ __global__ __launch_bounds__(kRuThreads) void k_ru_accum(const RuArgs A) {
     }
     long long matched = 0, no_time = 0, full = 0;
     for (int64_t tile = blockIdx.x; tile < A.n_tiles; tile += gridDim.x) {
-        const RowBlk B = A.blk[block_of(A.blk, A.nb, tile, &RowBlk::base)];  // (uniform, scalar)
-        const int64_t p0 = B.start + (tile - B.base) * kRuTileRows + (int64_t)tid * kRuRows;
-        const int64_t left = B.start + B.n - p0;
-        uint32_t m = left <= 0 ? 0u : left >= kRuRows ? 0xFu : (1u << (int)left) - 1u;  // the lane's live rows ...
-        if (A.bits != nullptr && m != 0) m &= A.bits[p0 >> 5] >> (p0 & 31);               // ... that pass the filters
-        matched += __popc(m);
-
-        // ---- the composite key
-        uint64_t comp[kRuRows] = {0, 0, 0, 0};
-        for (int g = 0; g < A.n_keys; g++) {
-            int64_t v[kRuRows];
-            const uint32_t pop = ru_load(A.keys[g], p0, m, v);
-            const int64_t lo = A.key_lo[g];
-            const uint64_t stride = A.key_stride[g];
-            if (g == 0 && A.has_time) {
-                no_time += __popc(m & ~pop);
-                m &= pop;
-#pragma unroll
-                for (int k = 0; k < kRuRows; k++)
-                    if ((m >> k) & 1u) comp[k] += (uint64_t)(v[k] / A.time_bucket - lo) * stride;
-            } else {
-                const uint64_t miss = (uint64_t)A.keys[g].missing;
-                if (!miss) m &= pop;  // (a column without a bitmap has every row populated)
-#pragma unroll
-                for (int k = 0; k < kRuRows; k++)
-                    if ((pop >> k) & 1u) comp[k] += ((uint64_t)v[k] - (uint64_t)lo + miss) * stride;
-            }
-        }
-
-        // ---- the cell: the composite itself, or its slot; a lane's consecutive rows of one key probe once
-        uint32_t cell[kRuRows] = {0, 0, 0, 0};
-#pragma unroll
-        for (int k = 0; k < kRuRows; k++) {
-            if (!((m >> k) & 1u)) continue;
-            if (HASH) {
-                if (k > 0 && ((m >> (k - 1)) & 1u) && comp[k] == comp[k - 1]) {
-                    cell[k] = cell[k - 1];
-                    continue;
-                }
-                const int32_t s = ru_find_or_claim(A.hkeys, A.hmask, comp[k]);
-                if (s < 0) {
-                    full++;
-                    m &= ~(1u << k);
-                } else {
-                    cell[k] = (uint32_t)s;
-                }
-            } else if (comp[k] >= (uint64_t)n_cells) {
-                m &= ~(1u << k);  // (beyond the tracked extrema: cannot be; never an address)
-            } else {
-                cell[k] = (uint32_t)comp[k];
-            }
-        }
+        int64_t p0;
+        uint32_t cell[kRuRows];
+        const uint32_t m = ru_rows<HASH, true>(A, tile, tid, &p0, cell, &matched, &no_time, &full);
         const unsigned long long act = __ballot(m != 0);
         if (act == 0) continue;  // (the whole wave filtered out; no barrier inside the loop)
 
@@ -359,6 +396,114 @@ __global__ __launch_bounds__(kRuThreads) void k_ru_slot_keys(const uint64_t *__r
     if (i < n) out[i] = hkeys[slots[i]];
 }
 
+// ---- percentiles: the sort keys of one aggregated column.  The front end is k_ru_accum's; a matching row whose value is
+// populated is an item.  Items are compacted: per row slot a wave ballot ranks the lanes, the workgroup's four wave totals meet in
+// LDS and ONE cursor atomic per workgroup and tile reserves the tile's range -- the order of items before the sort is free, the
+// keys alone determine the result.  The buffers hold M items: an item at or beyond M is dropped and counted, as is a row whose
+// composite is not in the table (neither can be; neither becomes an address).
+struct RuPct {
+    RuCol val;
+    uint64_t lo, vmask;  // key = cell << vbits | ((v - lo) & vmask)
+    int32_t vbits;
+    void *keys;          // [M] uint32 (V = 32) or uint64; <pairs>: (v - lo) & vmask alone
+    uint32_t *cells;     // <pairs>: [M] the payload
+    long long *cursor;   // zeroed
+    long long *dropped;
+    int64_t M;
+};
+
+template <bool HASH, int V>
+__global__ __launch_bounds__(kRuThreads) void k_ru_pct_keys(const RuArgs A, const RuPct P) {
+    __shared__ int wsum[kRuThreads / 64];
+    __shared__ long long sbase;
+    const int tid = (int)threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const unsigned long long below = (1ull << lane) - 1ull;
+    long long matched = 0, no_time = 0, dropped = 0;
+    for (int64_t tile = blockIdx.x; tile < A.n_tiles; tile += gridDim.x) {  // (uniform: every wave reaches both barriers)
+        int64_t p0;
+        uint32_t cell[kRuRows];
+        const uint32_t m = ru_rows<HASH, false>(A, tile, tid, &p0, cell, &matched, &no_time, &dropped);
+        int64_t v[kRuRows];
+        const uint32_t pop = ru_load(P.val, p0, m, v);
+        int rank[kRuRows], wtotal = 0;
+#pragma unroll
+        for (int k = 0; k < kRuRows; k++) {
+            const unsigned long long b = __ballot((pop >> k) & 1u);
+            rank[k] = wtotal + __popcll(b & below);
+            wtotal += __popcll(b);
+        }
+        if (lane == 0) wsum[wave] = wtotal;
+        __syncthreads();
+        int before = 0, total = 0;
+#pragma unroll
+        for (int w = 0; w < kRuThreads / 64; w++) {
+            const int s = wsum[w];
+            before += w < wave ? s : 0;
+            total += s;
+        }
+        if (tid == 0) sbase = total > 0 ? __hip_atomic_fetch_add(P.cursor, (long long)total, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+        __syncthreads();
+        const int64_t base = (int64_t)sbase + before;
+#pragma unroll
+        for (int k = 0; k < kRuRows; k++) {
+            if (!((pop >> k) & 1u)) continue;
+            const int64_t at = base + rank[k];
+            if (at < 0 || at >= P.M) {
+                dropped++;
+                continue;
+            }
+            const uint64_t d = ((uint64_t)v[k] - P.lo) & P.vmask;
+            const uint64_t major = P.vbits < 64 ? (uint64_t)cell[k] << P.vbits : 0;  // (64 value bits: one cell, cell 0)
+            if (V == 32) {
+                ((uint32_t *)P.keys)[at] = (uint32_t)(major | d);
+            } else if (V == 64) {
+                ((uint64_t *)P.keys)[at] = major | d;
+            } else {
+                ((uint64_t *)P.keys)[at] = d;
+                P.cells[at] = cell[k];
+            }
+        }
+    }
+    dropped = ru_wave_sum(dropped);
+    if (lane == 0 && dropped) __hip_atomic_fetch_add(P.dropped, dropped, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// ---- percentiles: the pick.  A lane per (output row g, percentile): c the g-th occupied cell of the order phase, n = n[c] its
+// populated values, off = offsets[c] where they start in the sorted array; the value of 1-based rank (k * n + 99) / 100, as
+// lo + (key & vmask) with wrapping unsigned addition, into [percentile][G].  n = 0: 0 (the emit leaves it unpopulated).
+struct RuPick {
+    const uint32_t *cell;  // [G]
+    const int64_t *n;      // [n_cells] the column's n field
+    const int64_t *off;    // [n_cells] its exclusive sum
+    const void *sorted;    // [M] uint32 / uint64 (wide)
+    int64_t *out;          // [np][G]
+    long long *dropped;
+    int64_t G, M;
+    uint64_t lo, vmask;
+    int32_t np, wide;
+    int32_t k[kRuMaxPcts];
+};
+
+__global__ __launch_bounds__(kRuThreads) void k_ru_pct_pick(const RuPick P) {
+    const int64_t i = (int64_t)blockIdx.x * kRuThreads + threadIdx.x;
+    if (i >= P.G * P.np) return;
+    const int p = (int)(i / P.G);
+    const int64_t g = i - (int64_t)p * P.G;
+    const uint32_t c = P.cell[g];
+    const int64_t n = P.n[c];
+    int64_t r = 0;
+    if (n > 0) {
+        const int64_t at = P.off[c] + ((int64_t)P.k[p] * n + 99) / 100 - 1;
+        if (at < 0 || at >= P.M) {
+            __hip_atomic_fetch_add(P.dropped, 1ll, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // (cannot be; never an address)
+        } else {
+            const uint64_t key = P.wide ? ((const uint64_t *)P.sorted)[at] : (uint64_t)((const uint32_t *)P.sorted)[at];
+            r = (int64_t)(P.lo + (key & P.vmask));
+        }
+    }
+    P.out[i] = r;
+}
+
 struct RuOccupied {
     __host__ __device__ __forceinline__ bool operator()(const int64_t &count) const { return count > 0; }
 };
@@ -367,7 +512,7 @@ struct RuClaimed {
 };
 
 // ---- emit
-enum RuKind { kRuTime = 0, kRuGroup = 1, kRuField = 2, kRuFieldIfN = 3, kRuMinIfN = 4 };
+enum RuKind { kRuTime = 0, kRuGroup = 1, kRuField = 2, kRuFieldIfN = 3, kRuMinIfN = 4, kRuArrayIfN = 5 };
 
 struct RuEmit {
     const uint32_t *cell;   // [G] the cell / slot of output row i, in key order
@@ -378,6 +523,7 @@ struct RuEmit {
     uint64_t kstride, radix;  // a key column: digit = composite / kstride % radix
     int64_t lo, bucket;
     int64_t f_off, n_off;  // a field: its offset in `cells`, and that of the column's n
+    const int64_t *arr;    // an array by output row (a percentile): [G]
     void *out;             // store pass
     uint32_t *out_valid;   // ... nullptr: the column has no bitmap
     int64_t out_base;
@@ -398,6 +544,10 @@ __device__ __forceinline__ bool ru_value(const RuEmit &E, int64_t i, int64_t *v)
         return true;
     }
     if (E.kind != kRuField && E.cells[E.n_off + cell] <= 0) return false;
+    if (E.kind == kRuArrayIfN) {
+        *v = E.arr[i];
+        return true;
+    }
     const int64_t f = E.cells[E.f_off + cell];
     *v = E.kind == kRuMinIfN ? ~f : f;
     return true;
@@ -487,6 +637,12 @@ constexpr const char *kWho = "sybl_table_rollup";
 struct AggPlan {
     Column *c = nullptr;
     bool want[4] = {false, false, false, false};  // n, sum, min, max
+    std::vector<int> pcts;                        // the k of its p<k> tokens, ascending
+    // percentiles: what the host plan decided (variant 0: no populated value, nothing to sort) and where the values land
+    int variant = kRuPctNone, cbits = 0, vbits = 0;
+    int64_t M = 0;
+    int64_t *picked = nullptr;  // [pcts][G]
+    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
 };
 
 // an output column: where its values come from
@@ -496,7 +652,7 @@ struct OutCol {
     RuEmit E{};
 };
 
-bool parse_ops(const char *ops, bool want[4]) {
+bool parse_ops(const char *ops, bool want[4], std::vector<int> *pcts) {
     static const char *const names[4] = {"n", "sum", "min", "max"};
     if (!ops || !ops[0]) return false;
     const char *p = ops;
@@ -506,11 +662,19 @@ bool parse_ops(const char *ops, bool want[4]) {
         int hit = -1;
         for (int k = 0; k < 4; k++)
             if (strlen(names[k]) == len && !strncmp(names[k], p, len)) hit = k;
-        if (hit < 0 || want[hit]) return false;
-        want[hit] = true;
-        if (!e) return true;
+        if (hit >= 0) {
+            if (want[hit]) return false;
+            want[hit] = true;
+        } else {
+            const int k = ru_pct_token(p, len);
+            if (k == 0 || std::find(pcts->begin(), pcts->end(), k) != pcts->end() || pcts->size() >= (size_t)kRuMaxPcts) return false;
+            pcts->push_back(k);
+        }
+        if (!e) break;
         p = e + 1;
     }
+    std::sort(pcts->begin(), pcts->end());
+    return true;
 }
 
 RuCol col_view(const Column *c, bool missing) {
@@ -533,7 +697,7 @@ void launch_emit(bool store, int width, const RuEmit &E, hipStream_t st) {
     else by_width(width, [&](auto W) { hipLaunchKernelGGL((k_ru_emit<true, decltype(W)::value>), g, b, 0, st, E); });
 }
 
-int run(Table *t, const sybl_rollup_desc *d, int64_t block_rows, Table *o, sybl_rollup_stats *S) {
+int run(Table *t, const sybl_rollup_desc *d, int64_t block_rows, Table *o, sybl_rollup_stats *S, sybl_rollup_pct_stats *PS) {
     Ctx *ctx = t->ctx;
     hipStream_t st = ctx->stream;
     int rc;
@@ -578,11 +742,24 @@ int run(Table *t, const sybl_rollup_desc *d, int64_t block_rows, Table *o, sybl_
         if (!c) return fail(SYBL_E_INVAL, "%s: unknown aggregated column '%s'", kWho, name ? name : "(null)");
         if (c->type != SYBL_INT_VAL) return fail(SYBL_E_INVAL, "%s: aggregated column '%s' is a %s column; n, sum, min and max are taken of int columns", kWho, name, type_name(c->type));
         aggs[(size_t)i].c = c;
-        if (!parse_ops(d->aggs[i].ops, aggs[(size_t)i].want))
-            return fail(SYBL_E_INVAL, "%s: column '%s': ops '%s' are not a non-empty subset of n, sum, min, max", kWho, name, d->aggs[i].ops ? d->aggs[i].ops : "(null)");
+        if (!parse_ops(d->aggs[i].ops, aggs[(size_t)i].want, &aggs[(size_t)i].pcts))
+            return fail(SYBL_E_INVAL, "%s: column '%s': ops '%s' are not a non-empty subset of n, sum, min, max and at most %d of p1 .. p99", kWho, name,
+                        d->aggs[i].ops ? d->aggs[i].ops : "(null)", kRuMaxPcts);
         for (int k = 0; k < 4; k++)
             if (aggs[(size_t)i].want[k] && !claim(c->name + suffix[k]))
                 return fail(SYBL_E_INVAL, "%s: column '%s%s': the output already holds a column of that name", kWho, name, suffix[k]);
+        for (int k : aggs[(size_t)i].pcts)
+            if (!claim(c->name + "_p" + std::to_string(k)))
+                return fail(SYBL_E_INVAL, "%s: column '%s_p%d': the output already holds a column of that name", kWho, name, k);
+        if (!aggs[(size_t)i].pcts.empty()) {
+            PS->columns++;
+            PS->percentiles += (int32_t)aggs[(size_t)i].pcts.size();
+        }
+    }
+    int pct_force = kRuPctNone;
+    if (const char *e = env("SYBL_ROLLUP_PCT")) {
+        pct_force = !strcmp(e, "32") ? kRuPct32 : !strcmp(e, "64") ? kRuPct64 : !strcmp(e, "pairs") ? kRuPctPairs : -1;
+        if (pct_force < 0) return fail(SYBL_E_INVAL, "%s: SYBL_ROLLUP_PCT=%s is none of 32, 64, pairs", kWho, e);
     }
     int force = kRuForceNone;
     if (const char *e = env("SYBL_ROLLUP_PATH")) {
@@ -644,7 +821,8 @@ int run(Table *t, const sybl_rollup_desc *d, int64_t block_rows, Table *o, sybl_
     for (Column *c : gcols) outs[add_col(c->name, c)].E.kind = kRuGroup;
     const size_t count_at = add_col(count_name, nullptr);
     outs[count_at].E.kind = kRuField;
-    for (int a = 0; a < n_vals; a++)
+    std::vector<std::pair<size_t, int>> pct_outs;  // (output column, aggregated column): the percentiles, in output order
+    for (int a = 0; a < n_vals; a++) {
         for (int k = 0; k < 4; k++) {
             if (!aggs[(size_t)a].want[k]) continue;
             RuEmit &E = outs[add_col(aggs[(size_t)a].c->name + suffix[k], nullptr)].E;
@@ -653,6 +831,13 @@ int run(Table *t, const sybl_rollup_desc *d, int64_t block_rows, Table *o, sybl_
             E.f_off = 1 + 4 * a + (k == 0 ? 0 : k == 1 ? 1 : k == 2 ? 3 : 2);  // (a field number until the cells are sized)
             E.n_off = 1 + 4 * a;
         }
+        for (int k : aggs[(size_t)a].pcts) {  // after the column's four, ascending k
+            const size_t at = add_col(aggs[(size_t)a].c->name + "_p" + std::to_string(k), nullptr);
+            outs[at].E.kind = kRuArrayIfN;
+            outs[at].E.n_off = 1 + 4 * a;
+            pct_outs.emplace_back(at, a);
+        }
+    }
 
     // ---- the source rows: the live blocks, a tile = 1024 rows of one block
     std::vector<RowBlk> blk;
@@ -702,20 +887,32 @@ int run(Table *t, const sybl_rollup_desc *d, int64_t block_rows, Table *o, sybl_
     S->path = path;
     S->cells_or_slots = n_cells;
     for (int a = 0; a < n_vals; a++) A.vals[a] = col_view(aggs[(size_t)a].c, false);
+    // percentiles: the sort key of every column that has a populated value -- cell above, v - lo below -- and its variant
+    for (AggPlan &ap : aggs) {
+        if (ap.pcts.empty() || ap.c->n_pop <= 0) continue;  // (no populated value: nothing to sort, every percentile unpopulated)
+        ap.cbits = ru_pct_cbits(n_cells);
+        ap.vbits = ru_pct_vbits(ap.c->exact_min, ap.c->exact_max);
+        ap.variant = ru_pct_variant(ap.cbits, ap.vbits, pct_force);
+        if (ap.variant == kRuPctNone)
+            return fail(SYBL_E_INVAL, "%s: SYBL_ROLLUP_PCT=%s holds fewer bits than the %d + %d of the cell and the values of column '%s'", kWho,
+                        env("SYBL_ROLLUP_PCT"), ap.cbits, ap.vbits, ap.c->name.c_str());
+    }
 
     GatherPool pool;
     hipEvent_t ev[5];
     RowBlk *d_blk = nullptr;
-    long long *d_ctr = nullptr;  // matched, rows_no_time, full, G
+    // matched, rows_no_time, full, G; percentiles: items dropped, then per aggregated column its items M and its cursor
+    constexpr int kCtrDropped = 4, kCtrM = 5, kCtrCursor = kCtrM + kRuMaxAggs, kCtrs = kCtrCursor + kRuMaxAggs;
+    long long *d_ctr = nullptr;
     int64_t *cells = nullptr;
     uint64_t *hkeys = nullptr;
     uint32_t *bits = nullptr;
     if ((rc = pool.alloc(&d_blk, blk.size(), "rollup blocks"))) return rc;
-    if ((rc = pool.alloc(&d_ctr, 4, "rollup counters"))) return rc;
+    if ((rc = pool.alloc(&d_ctr, kCtrs, "rollup counters"))) return rc;
     if ((rc = pool.alloc(&cells, (size_t)fields * (size_t)n_cells, "rollup cells"))) return rc;
     if (path == kRuPathHash && (rc = pool.alloc(&hkeys, (size_t)n_cells, "rollup hash keys"))) return rc;
     if ((rc = host_to_device(ctx, d_blk, blk.data(), blk.size() * sizeof(RowBlk), "rollup blocks"))) return rc;
-    SYBL_HIP(hipMemsetAsync(d_ctr, 0, 4 * sizeof(long long), st));
+    SYBL_HIP(hipMemsetAsync(d_ctr, 0, kCtrs * sizeof(long long), st));
 
     // ---- filter
     if ((rc = pool.event(&ev[0], st))) return rc;
@@ -798,7 +995,17 @@ int run(Table *t, const sybl_rollup_desc *d, int64_t block_rows, Table *o, sybl_
     if ((rc = pool.alloc(&tmp, tmp_bytes, "rollup order"))) return rc;
     if (hkeys) SYBL_HIP(hipcub::DeviceSelect::Flagged(tmp, tmp_bytes, idx, claimed, d_cell, d_ctr + 3, (int)n_cells, st));
     else SYBL_HIP(hipcub::DeviceSelect::Flagged(tmp, tmp_bytes, idx, occupied, d_cell, d_ctr + 3, (int)n_cells, st));
-    long long ctr[4] = {0, 0, 0, 0};
+    // percentiles: the items of every column to sort, M = the sum of its n field over the cells, travel with the same readback
+    for (int a = 0; a < n_vals; a++) {
+        if (aggs[(size_t)a].variant == kRuPctNone) continue;
+        const int64_t *n_field = cells + (int64_t)(1 + 4 * a) * n_cells;
+        size_t red_bytes = 0;
+        char *red_tmp = nullptr;
+        SYBL_HIP(hipcub::DeviceReduce::Sum(nullptr, red_bytes, n_field, d_ctr + kCtrM + a, (int)n_cells, st));
+        if ((rc = pool.alloc(&red_tmp, red_bytes, "rollup percentile items"))) return rc;
+        SYBL_HIP(hipcub::DeviceReduce::Sum(red_tmp, red_bytes, n_field, d_ctr + kCtrM + a, (int)n_cells, st));
+    }
+    long long ctr[kCtrCursor] = {0};
     SYBL_HIP(hipMemcpyAsync(ctr, d_ctr, sizeof(ctr), hipMemcpyDeviceToHost, st));  // the one readback: the counters and G
     SYBL_HIP(hipStreamSynchronize(st));
     S->rows_matched = ctr[0];
@@ -837,6 +1044,148 @@ int run(Table *t, const sybl_rollup_desc *d, int64_t block_rows, Table *o, sybl_
         return SYBL_OK;
     }
 
+    // ---- percentiles, once per aggregated column that has some: offsets, keys, sort, pick.  Every column uses the same buffers;
+    // one sort serves all percentiles of a column.
+    const uint32_t *out_cell = hkeys ? d_cell2 : d_cell;
+    hipEvent_t ev_emit = ev[3];
+    {
+        size_t key_bytes = 0, pay_bytes = 0, work_bytes = 0;
+        int64_t *d_off = nullptr;
+        char *keys_a = nullptr, *keys_b = nullptr, *work = nullptr;
+        uint32_t *pay_a = nullptr, *pay_b = nullptr;
+        bool any = false;
+        // what the hipcub calls below need, at their largest over the columns
+        for (int a = 0; a < n_vals; a++) {
+            AggPlan &ap = aggs[(size_t)a];
+            if (ap.pcts.empty()) continue;
+            if ((rc = pool.alloc(&ap.picked, ap.pcts.size() * (size_t)G, "rollup percentiles"))) return rc;
+            ap.M = ap.variant == kRuPctNone ? 0 : ctr[kCtrM + a];
+            if (ap.M < 0 || ap.M > N) return fail(SYBL_E_STATE, "%s: %lld values to sort among %lld rows", kWho, (long long)ap.M, (long long)N);
+            if (ap.M > (int64_t)INT32_MAX)
+                return fail(SYBL_E_INVAL, "%s: column '%s': %lld values to sort; the percentile sort takes at most 2^31 - 1", kWho, ap.c->name.c_str(), (long long)ap.M);
+            if (ap.M == 0) continue;
+            any = true;
+            const int M = (int)ap.M, kbits = std::max(1, ap.cbits + ap.vbits);
+            size_t need = 0;
+            SYBL_HIP(hipcub::DeviceScan::ExclusiveSum(nullptr, need, (const int64_t *)nullptr, (int64_t *)nullptr, (int)n_cells, st));
+            work_bytes = std::max(work_bytes, need);
+            if (ap.variant == kRuPct32) {
+                SYBL_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, need, (const uint32_t *)nullptr, (uint32_t *)nullptr, M, 0, kbits, st));
+                work_bytes = std::max(work_bytes, need);
+            } else if (ap.variant == kRuPct64) {
+                SYBL_HIP(hipcub::DeviceRadixSort::SortKeys(nullptr, need, (const uint64_t *)nullptr, (uint64_t *)nullptr, M, 0, kbits, st));
+                work_bytes = std::max(work_bytes, need);
+            } else {
+                SYBL_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, need, (const uint64_t *)nullptr, (uint64_t *)nullptr, (const uint32_t *)nullptr,
+                                                            (uint32_t *)nullptr, M, 0, std::max(1, ap.vbits), st));
+                work_bytes = std::max(work_bytes, need);
+                SYBL_HIP(hipcub::DeviceRadixSort::SortPairs(nullptr, need, (const uint32_t *)nullptr, (uint32_t *)nullptr, (const uint64_t *)nullptr,
+                                                            (uint64_t *)nullptr, M, 0, std::max(1, ap.cbits), st));
+                work_bytes = std::max(work_bytes, need);
+                pay_bytes = std::max(pay_bytes, (size_t)M * 4);
+            }
+            key_bytes = std::max(key_bytes, (size_t)M * (ap.variant == kRuPct32 ? 4 : 8));
+        }
+        if (any) {
+            if ((rc = pool.alloc(&d_off, (size_t)n_cells, "rollup percentile offsets"))) return rc;
+            if ((rc = pool.alloc(&keys_a, key_bytes, "rollup percentile keys"))) return rc;
+            if ((rc = pool.alloc(&keys_b, key_bytes, "rollup percentile keys"))) return rc;
+            if (pay_bytes > 0 && (rc = pool.alloc(&pay_a, pay_bytes / 4, "rollup percentile keys"))) return rc;
+            if (pay_bytes > 0 && (rc = pool.alloc(&pay_b, pay_bytes / 4, "rollup percentile keys"))) return rc;
+            if ((rc = pool.alloc(&work, work_bytes, "rollup percentile sort"))) return rc;
+        }
+        int64_t key_cols_bytes = bits ? ((row_hi + 31) >> 5) * 4 : 0;
+        for (int k = 0; k < n_keys; k++) key_cols_bytes += col_bytes(k == 0 && tc ? tc : gcols[(size_t)(k - (tc ? 1 : 0))], N);
+        for (int a = 0; a < n_vals; a++) {
+            AggPlan &ap = aggs[(size_t)a];
+            if (ap.pcts.empty()) continue;
+            if (ap.M == 0) {  // (no value passed: every percentile is unpopulated, the emit reads none of them)
+                SYBL_HIP(hipMemsetAsync(ap.picked, 0, ap.pcts.size() * (size_t)G * 8, st));
+                continue;
+            }
+            const int M = (int)ap.M, kbits = std::max(1, ap.cbits + ap.vbits);
+            const int64_t *n_field = cells + (int64_t)(1 + 4 * a) * n_cells;
+            const int64_t item = ap.variant == kRuPct32 ? 4 : ap.variant == kRuPct64 ? 8 : 12;
+            // -- offsets and keys
+            if ((rc = pool.event(&ap.ev[0], st))) return rc;
+            size_t need = work_bytes;
+            SYBL_HIP(hipcub::DeviceScan::ExclusiveSum(work, need, n_field, d_off, (int)n_cells, st));
+            RuPct P{};
+            P.val = A.vals[a];
+            P.lo = (uint64_t)ap.c->exact_min;
+            P.vbits = ap.vbits;
+            P.vmask = ap.vbits >= 64 ? ~0ull : (1ull << ap.vbits) - 1ull;
+            P.keys = keys_a;
+            P.cells = pay_a;
+            P.cursor = d_ctr + kCtrCursor + a;
+            P.dropped = d_ctr + kCtrDropped;
+            P.M = ap.M;
+            {
+                const dim3 g((unsigned)std::max<int64_t>(1, std::min<int64_t>(n_tiles, (int64_t)std::max(ctx->n_cus, 1) * kRuWgPerCu))), b(kRuThreads);
+                const bool hash = hkeys != nullptr;
+                if (ap.variant == kRuPct32) {
+                    if (hash) hipLaunchKernelGGL((k_ru_pct_keys<true, 32>), g, b, 0, st, A, P);
+                    else hipLaunchKernelGGL((k_ru_pct_keys<false, 32>), g, b, 0, st, A, P);
+                } else if (ap.variant == kRuPct64) {
+                    if (hash) hipLaunchKernelGGL((k_ru_pct_keys<true, 64>), g, b, 0, st, A, P);
+                    else hipLaunchKernelGGL((k_ru_pct_keys<false, 64>), g, b, 0, st, A, P);
+                } else {
+                    if (hash) hipLaunchKernelGGL((k_ru_pct_keys<true, 0>), g, b, 0, st, A, P);
+                    else hipLaunchKernelGGL((k_ru_pct_keys<false, 0>), g, b, 0, st, A, P);
+                }
+                SYBL_HIP(hipGetLastError());
+            }
+            if ((rc = pool.event(&ap.ev[1], st))) return rc;
+            // -- sort: exactly the key's bits
+            const void *sorted = keys_b;
+            int64_t passes = (kbits + 7) / 8;
+            need = work_bytes;
+            if (ap.variant == kRuPct32) {
+                SYBL_HIP(hipcub::DeviceRadixSort::SortKeys(work, need, (const uint32_t *)keys_a, (uint32_t *)keys_b, M, 0, kbits, st));
+            } else if (ap.variant == kRuPct64) {
+                SYBL_HIP(hipcub::DeviceRadixSort::SortKeys(work, need, (const uint64_t *)keys_a, (uint64_t *)keys_b, M, 0, kbits, st));
+            } else {
+                // by value with the cell as payload, then by cell carrying the value: the radix sort is STABLE, so within a cell the
+                // values keep the ascending order of the first sort
+                SYBL_HIP(hipcub::DeviceRadixSort::SortPairs(work, need, (const uint64_t *)keys_a, (uint64_t *)keys_b, (const uint32_t *)pay_a, pay_b, M, 0,
+                                                            std::max(1, ap.vbits), st));
+                need = work_bytes;
+                SYBL_HIP(hipcub::DeviceRadixSort::SortPairs(work, need, (const uint32_t *)pay_b, pay_a, (const uint64_t *)keys_b, (uint64_t *)keys_a, M, 0,
+                                                            std::max(1, ap.cbits), st));
+                sorted = keys_a;
+                passes = (std::max(1, ap.vbits) + 7) / 8 + (std::max(1, ap.cbits) + 7) / 8;
+            }
+            if ((rc = pool.event(&ap.ev[2], st))) return rc;
+            // -- pick
+            RuPick K{};
+            K.cell = out_cell;
+            K.n = n_field;
+            K.off = d_off;
+            K.sorted = sorted;
+            K.out = ap.picked;
+            K.dropped = d_ctr + kCtrDropped;
+            K.G = G;
+            K.M = ap.M;
+            K.lo = P.lo;
+            K.vmask = ap.variant == kRuPctPairs ? ~0ull : P.vmask;
+            K.np = (int32_t)ap.pcts.size();
+            K.wide = ap.variant == kRuPct32 ? 0 : 1;
+            for (size_t k = 0; k < ap.pcts.size(); k++) K.k[k] = ap.pcts[k];
+            hipLaunchKernelGGL(k_ru_pct_pick, dim3(grid_for(G * K.np, kRuThreads)), dim3(kRuThreads), 0, st, K);
+            SYBL_HIP(hipGetLastError());
+            if ((rc = pool.event(&ap.ev[3], st))) return rc;
+            ev_emit = ap.ev[3];
+            // -- the counts, and the bytes from the shapes
+            PS->items += ap.M;
+            PS->key_bits_max = std::max<int32_t>(PS->key_bits_max, ap.cbits + ap.vbits);
+            (ap.variant == kRuPct32 ? PS->variant32 : ap.variant == kRuPct64 ? PS->variant64 : PS->variant_pairs)++;
+            PS->keys_bytes += 2 * n_cells * 8 + key_cols_bytes + col_bytes(ap.c, N) + ap.M * item;
+            // (an LSD pass per 8 bits reads and writes every item; the histogram pass reads the keys once more)
+            PS->sort_bytes += passes * 2 * ap.M * item + ap.M * (item == 12 ? 12 : item);
+            PS->pick_bytes += G * 4 + (int64_t)K.np * G * (8 + 8 + (K.wide ? 8 : 4) + 8);
+        }
+    }
+
     // ---- emit: the output's layout, block j at physical row j * stride
     const int64_t stride = round_up(block_rows, 32);
     const int64_t nb_out = (G + block_rows - 1) / block_rows;
@@ -849,10 +1198,14 @@ int run(Table *t, const sybl_rollup_desc *d, int64_t block_rows, Table *o, sybl_
     std::vector<long long> h_acc(3 * nc, 0);
     for (size_t c = 0; c < nc; c++) h_acc[3 * c] = INT64_MAX, h_acc[3 * c + 1] = INT64_MIN;
     if ((rc = host_to_device(ctx, d_acc, h_acc.data(), h_acc.size() * sizeof(long long), "rollup extrema"))) return rc;
+    {
+        std::vector<size_t> seen((size_t)n_vals, 0);  // percentile output columns are in (column, ascending k) order
+        for (const auto &po : pct_outs) outs[po.first].E.arr = aggs[(size_t)po.second].picked + (int64_t)(seen[(size_t)po.second]++) * G;
+    }
     kk = 0;
     for (size_t c = 0; c < nc; c++) {
         RuEmit &E = outs[c].E;
-        E.cell = hkeys ? d_cell2 : d_cell;
+        E.cell = out_cell;
         E.comp = hkeys ? d_comp2 : nullptr;
         E.cells = cells;
         E.G = G;
@@ -875,7 +1228,11 @@ int run(Table *t, const sybl_rollup_desc *d, int64_t block_rows, Table *o, sybl_
         SYBL_HIP(hipGetLastError());
     }
     SYBL_HIP(hipMemcpyAsync(h_acc.data(), d_acc, h_acc.size() * sizeof(long long), hipMemcpyDeviceToHost, st));  // read back once
+    long long pct_dropped = 0;  // (with the same wait)
+    if (!pct_outs.empty()) SYBL_HIP(hipMemcpyAsync(&pct_dropped, d_ctr + kCtrDropped, sizeof(long long), hipMemcpyDeviceToHost, st));
     SYBL_HIP(hipStreamSynchronize(st));
+    if (pct_dropped != 0)
+        return fail(SYBL_E_STATE, "%s: internal error: %lld percentile items had no place in the sorted values", kWho, pct_dropped);
     std::vector<Column *> made;
     for (size_t c = 0; c < nc; c++) {
         OutCol &oc = outs[c];
@@ -912,8 +1269,17 @@ int run(Table *t, const sybl_rollup_desc *d, int64_t block_rows, Table *o, sybl_
     S->accumulate_ms = f;
     SYBL_HIP(hipEventElapsedTime(&f, ev[2], ev[3]));
     S->order_ms = f;
-    SYBL_HIP(hipEventElapsedTime(&f, ev[3], ev[4]));
+    SYBL_HIP(hipEventElapsedTime(&f, ev_emit, ev[4]));
     S->emit_ms = f;
+    for (const AggPlan &ap : aggs) {
+        if (ap.ev[3] == nullptr) continue;
+        SYBL_HIP(hipEventElapsedTime(&f, ap.ev[0], ap.ev[1]));
+        PS->keys_ms += f;
+        SYBL_HIP(hipEventElapsedTime(&f, ap.ev[1], ap.ev[2]));
+        PS->sort_ms += f;
+        SYBL_HIP(hipEventElapsedTime(&f, ap.ev[2], ap.ev[3]));
+        PS->pick_ms += f;
+    }
     return SYBL_OK;
 }
 
@@ -926,7 +1292,7 @@ int rollup_run(Table *t, const sybl_rollup_desc *d, sybl_table **out) {
     TableOwner O;
     int rc = derived_new_table(t->ctx, t->name, kWho, O);
     if (rc) return rc;
-    rc = derived_call(t->ctx, kWho, O, out, [&] { return run(t, d, br, O.t, &O.t->rollup_stats); });
+    rc = derived_call(t->ctx, kWho, O, out, [&] { return run(t, d, br, O.t, &O.t->rollup_stats, &O.t->rollup_pct_stats); });
     if (rc) {  // (what the planner, the table and the runtime say on the way is this call's error too)
         const std::string msg = sybl_last_error();
         if (msg.compare(0, strlen(kWho), kWho) != 0) return fail(rc, "%s: %s", kWho, msg.c_str());
@@ -951,6 +1317,13 @@ int sybl_table_rollup_stats(const sybl_table *t, sybl_rollup_stats *out) {
     SYBL_API_GUARD(t);
     if (!t || !out) return fail(SYBL_E_INVAL, "sybl_table_rollup_stats: NULL argument");
     *out = t->rollup_stats;
+    return SYBL_OK;
+}
+
+int sybl_table_rollup_pct_stats(const sybl_table *t, sybl_rollup_pct_stats *out) {
+    SYBL_API_GUARD(t);
+    if (!t || !out) return fail(SYBL_E_INVAL, "sybl_table_rollup_pct_stats: NULL argument");
+    *out = t->rollup_pct_stats;
     return SYBL_OK;
 }
 

@@ -1,7 +1,9 @@
 // rollup_plan.h -- what sybl_table_rollup (rollup.hip) decides on the host before any kernel runs: the digit of every key
-// column, the mixed-radix composite key, the path and the size of the hash table.  Host only, no HIP, as colstats.h;
-// tests/rollup_host_main.cpp runs it under sanitizers.  Every quantity that can leave int64 is carried in 128 bits.
+// column, the mixed-radix composite key, the path and the size of the hash table, and for percentiles the sort key's bits and
+// the sort variant.  Host only, no HIP, as colstats.h; tests/rollup_host_main.cpp and tests/rollup_pct_host_main.cpp run it under
+// sanitizers.  Every quantity that can leave int64 is carried in 128 bits.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 namespace sybl {
@@ -93,5 +95,46 @@ inline int ru_key_bits(ru_u128 product) {
     while (bits < 64 && (top >> bits) != 0) bits++;
     return bits;
 }
+
+// ------------------------------------------------------------------ percentiles (p<k> in `ops`)
+// Per aggregated column with percentiles the populated values of the matching rows are sorted by the key
+// cell << vbits | (v - lo): cell the direct path's cell or the hash path's slot, [lo, hi] the column's tracked extrema.  A group's
+// values are then contiguous, ascending, and start at the exclusive sum of n over the cells before its own.
+
+constexpr int kRuMaxPcts = 8;  // percentile tokens per aggregated column
+
+enum RuPctVariant { kRuPctNone = 0, kRuPct32 = 1, kRuPct64 = 2, kRuPctPairs = 3 };
+
+// A token p<k>: k a decimal integer 1..99 without a leading zero.  0: not such a token.
+inline int ru_pct_token(const char *p, size_t len) {
+    if (len < 2 || len > 3 || p[0] != 'p' || p[1] < '1' || p[1] > '9') return 0;
+    if (len == 2) return p[1] - '0';
+    if (p[2] < '0' || p[2] > '9') return 0;
+    return (p[1] - '0') * 10 + (p[2] - '0');
+}
+
+inline int ru_bits_of(ru_u128 x) {
+    int bits = 0;
+    while (bits < 128 && (x >> bits) != 0) bits++;
+    return bits;
+}
+
+// the bits of n_cells - 1: one cell needs none
+inline int ru_pct_cbits(int64_t n_cells) { return n_cells > 1 ? ru_bits_of((ru_u128)(n_cells - 1)) : 0; }
+
+// the bits of hi - lo, carried in 128 bits: 0 for one value, 64 for the whole int64 range
+inline int ru_pct_vbits(int64_t lo, int64_t hi) { return hi > lo ? ru_bits_of((ru_u128)((__int128)hi - (__int128)lo)) : 0; }
+
+// 32: cbits + vbits <= 32, uint32 keys; 64: <= 64, uint64 keys; pairs: beyond -- the values sorted with the cell as payload, then
+// stably by cell.  force: SYBL_ROLLUP_PCT, kRuPctNone = the rule.  kRuPctNone: the forced variant does not hold the bits.
+inline int ru_pct_variant(int cbits, int vbits, int force) {
+    const int bits = cbits + vbits;
+    const int fit = bits <= 32 ? kRuPct32 : bits <= 64 ? kRuPct64 : kRuPctPairs;
+    if (force == kRuPctNone) return fit;
+    return force >= fit ? force : kRuPctNone;
+}
+
+// nearest rank: the 1-based rank of p<k> among n > 0 ascending values, ceil(k * n / 100) (n counts rows: k * n stays in int64)
+inline int64_t ru_pct_rank(int k, int64_t n) { return ((int64_t)k * n + 99) / 100; }
 
 }  // namespace sybl

@@ -390,8 +390,10 @@ class Table:
     def rollup(self, groups=(), aggs=(), filters=(), time_col=None, time_bucket=0, count_name="count", block_rows=0):
         """A group-by as a NEW resident table (sybl_table_rollup): one row per distinct key among the rows that pass `filters`,
         ascending by (time bucket, groups..), holding the key columns, `count_name` and, per aggregated column, those asked for
-        of <col>_n, <col>_sum, <col>_min, <col>_max.  groups: up to 4 int / str columns; aggs: a list of (column, "sum,min,max,n")
-        pairs, or a dict in insertion order; time_bucket > 0 makes time_col (None = "time") the first part of the key, cut
+        of <col>_n, <col>_sum, <col>_min, <col>_max and its percentiles <col>_p<k>.  groups: up to 4 int / str columns; aggs: a
+        list of (column, "sum,min,max,n,p50,p99") pairs, or a dict in insertion order -- p<k>, k = 1..99, up to 8 per column, is
+        the exact nearest-rank percentile of the group's populated values (rank ceil(k * n / 100) of them in ascending order),
+        sorted on the GPU (rollup_pct_stats()); time_bucket > 0 makes time_col (None = "time") the first part of the key, cut
         into buckets of that size.  This table is untouched; free both."""
         keep = []
         pairs = list(aggs.items()) if isinstance(aggs, dict) else [tuple(a) for a in aggs]
@@ -416,6 +418,13 @@ class Table:
         """Path, counts, device time and bytes of the phases of the rollup() that made this table (sybl_table_rollup_stats)."""
         st = N.RollupStats()
         N.check(N.lib().sybl_table_rollup_stats(self._h, C.byref(st)))
+        return st.as_dict()
+
+    def rollup_pct_stats(self):
+        """Columns, variants, items, device time and bytes of the percentiles of the rollup() that made this table
+        (sybl_table_rollup_pct_stats); zeros for any table that no percentile rollup made."""
+        st = N.RollupPctStats()
+        N.check(N.lib().sybl_table_rollup_pct_stats(self._h, C.byref(st)))
         return st.as_dict()
 
     def query(self, filters=(), groups=(), aggs=(), op="avg", hist_bucket=0, want_percentiles=True, time_col=None,

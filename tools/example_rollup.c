@@ -1,6 +1,7 @@
 /* example_rollup.c -- sybl_table_rollup through the sybl_* C ABI from plain C99: build a small resident table block by block,
- * roll it up by (hour, host) into a NEW resident table holding count and the n / sum / max of latency (pre-aggregation: the raw
- * table is freed, the rollup lives on), print its first rows, and save it in the reference's on-disk format.
+ * roll it up by (hour, host) into a NEW resident table holding count, the n / sum / max of latency and its exact p50 / p99
+ * (pre-aggregation: the raw table is freed, the rollup lives on), print its first rows, and save it in the reference's on-disk
+ * format.
  *
  *   gcc -std=c99 -Iinclude tools/example_rollup.c -Lsybil_amd -lsybilgpu -Wl,-rpath,$PWD/sybil_amd -o example_rollup
  *   ./example_rollup <output dir>
@@ -61,7 +62,7 @@ int main(int argc, char **argv) {
     const char *groups[1] = {"host"};
     sybl_rollup_agg agg;
     agg.col = "latency";
-    agg.ops = "n,sum,max";
+    agg.ops = "n,sum,max,p50,p99";
     sybl_rollup_desc d;
     memset(&d, 0, sizeof(d));
     d.n_groups = 1;
@@ -83,21 +84,31 @@ int main(int argc, char **argv) {
     printf("hourly by host: %lld groups of %lld matching rows in %lld blocks (path %d, %lld cells; accumulate %.3f ms, emit %.3f ms)\n",
            (long long)st.groups, (long long)st.rows_matched, (long long)st.blocks_out, (int)st.path, (long long)st.cells_or_slots,
            st.accumulate_ms, st.emit_ms);
+    sybl_rollup_pct_stats ps;
+    if (sybl_table_rollup_pct_stats(hourly, &ps)) return die("sybl_table_rollup_pct_stats");
+    printf("percentiles: %d columns of %lld sorted values with keys of %d bits (keys %.3f ms, sort %.3f ms, pick %.3f ms)\n", (int)ps.percentiles,
+           (long long)ps.items, (int)ps.key_bits_max, ps.keys_ms, ps.sort_ms, ps.pick_ms);
     const int64_t g = sybl_table_rows(hourly);
     int64_t *hour = malloc((size_t)g * sizeof(int64_t)), *count = malloc((size_t)g * sizeof(int64_t)), *sum = malloc((size_t)g * sizeof(int64_t));
-    if (!hour || !count || !sum) return 1;
+    int64_t *p50 = malloc((size_t)g * sizeof(int64_t)), *p99 = malloc((size_t)g * sizeof(int64_t));
+    if (!hour || !count || !sum || !p50 || !p99) return 1;
     if (sybl_table_read_int(hourly, "time", 0, g, hour) || sybl_table_read_int(hourly, "count", 0, g, count) ||
-        sybl_table_read_int(hourly, "latency_sum", 0, g, sum))
+        sybl_table_read_int(hourly, "latency_sum", 0, g, sum) || sybl_table_read_int(hourly, "latency_p50", 0, g, p50) ||
+        sybl_table_read_int(hourly, "latency_p99", 0, g, p99))
         return die("sybl_table_read_int");
     int64_t total = 0;
     for (int64_t i = 0; i < g; i++) {
         total += count[i];
-        if (i < 6) printf("  hour %lld: count %lld, latency_sum %lld\n", (long long)hour[i], (long long)count[i], (long long)sum[i]);
+        if (i < 6)
+            printf("  hour %lld: count %lld, latency_sum %lld, latency_p50 %lld, latency_p99 %lld\n", (long long)hour[i], (long long)count[i],
+                   (long long)sum[i], (long long)p50[i], (long long)p99[i]);
     }
     printf("counts add up to %lld\n", (long long)total);
     free(hour);
     free(count);
     free(sum);
+    free(p50);
+    free(p99);
     if (sybl_table_save(hourly, argv[1])) return die("sybl_table_save");
     printf("saved under %s/events\n", argv[1]);
 
