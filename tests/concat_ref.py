@@ -55,7 +55,12 @@ def merged_dict(dicts):
 
 
 def table_dict(blocks, name):
-    """The dictionary a table built block by block holds for a str / set column: its strings in first-seen order."""
+    """The dictionary a table built block by block holds for a str / set column: its strings in first-seen order.  A block list
+    that stands for a DERIVED table (tests/chain_ref.py: Blocks) carries the dictionaries its table inherited id for id, which
+    need not be in the first-seen order of its own rows; those win."""
+    carried = getattr(blocks, "dicts", None)
+    if carried is not None and name in carried:
+        return list(carried[name])
     out = []
     for _, cols in blocks:
         spec = cols.get(name)

@@ -112,7 +112,10 @@ def rollup_ref(blocks, groups=(), aggs=(), filters=(), time_col=None, time_bucke
     for g in groups:
         v, p = ints_of(g)
         pv = [x for x, ok in zip(v, p) if ok]
-        product *= max(1, (max(pv) - min(pv) + 1 if pv else 0) + (0 if all(p) and N else 1))
+        # the MISSING digit: where the column has a bitmap.  A table built block by block has one iff a row is unpopulated; a
+        # derived table says which of its columns have one (tests/chain_ref.py: Blocks.bitmap), unpopulated rows or not
+        digit = getattr(blocks, "bitmap", {}).get(g, not (all(p) and N))
+        product *= max(1, (max(pv) - min(pv) + 1 if pv else 0) + (1 if digit else 0))
         keys.append((v, p))
     stats = dict(rows_in=N, rows_matched=0, rows_no_time=0, groups=0, blocks_out=0, path=0, fields=fields, cells_or_slots=0)
     out = dict(columns=names, blocks=[], storage={}, bitmap={n: False for n, _ in names}, dicts=dicts, stats=stats, product=product)

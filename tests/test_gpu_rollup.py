@@ -52,12 +52,15 @@ def env(monkeypatch):
     return set_
 
 
-def _check(t, tl, compact, path=None, force=None, slots=0, rows=True, **kw):
+def _check(t, tl, compact, path=None, force=None, slots=0, rows=True, ref=None, rolled=False, **kw):
     """t.rollup(**kw) against rollup_ref: counts, columns, every row, storage, bitmaps, dictionaries, extrema, the stored values
-    of unpopulated rows, the untouched source.  Returns (table, stats, ref)."""
-    ref = U.rollup_ref(tl, compact=compact, force=force, slots=slots, **kw)
+    of unpopulated rows, the untouched source.  ref: the restatement's result where the caller has it; rolled: t is itself a
+    rollup's output (its own stats are then not zeros: they stay what they were).  Returns (table, stats, ref)."""
+    if ref is None:
+        ref = U.rollup_ref(tl, compact=compact, force=force, slots=slots, **kw)
     G = ref["stats"]["groups"]
     before = (t.rows, t.blocks)
+    own = t.rollup_stats()
     out = t.rollup(**kw)
     try:
         st = out.rollup_stats()
@@ -65,7 +68,7 @@ def _check(t, tl, compact, path=None, force=None, slots=0, rows=True, **kw):
         if path is not None:
             assert st["path"] == path, st
         assert (out.rows, out.blocks) == (G, len(ref["blocks"])) and (t.rows, t.blocks) == before
-        assert t.rollup_stats() == {k: 0 for k in st}                  # zeros for a table no rollup made
+        assert t.rollup_stats() == (own if rolled else {k: 0 for k in st})      # zeros for a table no rollup made
         assert out.samples(limit=1).columns == [c for c, _ in ref["columns"]]
         if rows:
             assert _rows(out) == D.rows_of(ref["blocks"])

@@ -52,7 +52,7 @@ def env(monkeypatch):
     return set_
 
 
-def _check(t, tl, compact, path=None, force=None, slots=0, pct=None, ref=None, **kw):
+def _check(t, tl, compact, path=None, force=None, slots=0, pct=None, ref=None, rolled=False, **kw):
     """t.rollup(**kw) against rollup_pct_ref: the counts of both stats, columns, every row, storage, bitmaps, extrema folded from
     the block statistics, the stored values of unpopulated rows, the order of the percentiles, the untouched source.  Returns
     (table, pct stats, ref)."""
@@ -60,6 +60,7 @@ def _check(t, tl, compact, path=None, force=None, slots=0, pct=None, ref=None, *
         ref = P.rollup_pct_ref(tl, compact=compact, force=force, slots=slots, pct_force=pct, **kw)
     G = ref["stats"]["groups"]
     before = (t.rows, t.blocks)
+    own = t.rollup_pct_stats()                                         # rolled: t is itself a percentile rollup's output
     out = t.rollup(**kw)
     try:
         st, ps = out.rollup_stats(), out.rollup_pct_stats()
@@ -68,7 +69,7 @@ def _check(t, tl, compact, path=None, force=None, slots=0, pct=None, ref=None, *
         if path is not None:
             assert st["path"] == path, st
         assert (out.rows, out.blocks) == (G, len(ref["blocks"])) and (t.rows, t.blocks) == before
-        assert t.rollup_pct_stats() == {k: 0 for k in ps}                              # zeros for a table no percentile rollup made
+        assert t.rollup_pct_stats() == (own if rolled else {k: 0 for k in ps})         # zeros for a table no percentile rollup made
         assert out.samples(limit=1).columns == [c for c, _ in ref["columns"]]
         assert _rows(out) == D.rows_of(ref["blocks"])
         cols = D.concat(ref["blocks"]) if G else {}
